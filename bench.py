@@ -17,8 +17,16 @@ draws S samples per step (weak scaling).  `--schedule replicas` keeps the
 replicated tables with the adaptive delta all-reduce (dist.ReplicaSync).
 Rank 0 prints one JSON line; n_gpus is the process group's world size.
 
-    python bench.py [--gpus N --steps K --warmup W]
-        (N > 1 without WORLD_SIZE: bench.py starts torch.distributed.run with
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+        (a plain run sets up, warms up, times the K steps and prints the line;
+         --full adds the measurements that take runs of their own: the live
+         rocprofv3 --pmc traffic, the device copy bandwidth, the CPU baseline
+         and the finite check of the whole table.
+         --dump-outputs DIR: after the timed steps, the last of them once more
+         from the seeded initial tables, every update kept; the W and C tables
+         it leaves as DIR/*.npy, the same from run to run up to the order of
+         the float adds.
+         N > 1 without WORLD_SIZE: bench.py starts torch.distributed.run with
          N ranks as a child process, relays its output and exits with its
          status; nothing here touches the GPU first)
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
@@ -95,13 +103,21 @@ def parse():
                     help="N > 1, --sync sum: hub rows per table exchanged after every launch")
     ap.add_argument("--launches", type=int, default=8,
                     help="N > 1: training launches per step, each followed by the hub-row exchange")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline.traffic live (--pmc), the device copy "
+                         "bandwidth (roofline.measured_peak), the CPU baseline, and check the whole W table finite")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps run the last of them once more from the seeded initial tables "
+                         "with the hot threshold at 0 (no update lost) and write the tables it leaves (a seeded "
+                         "sample of DUMP_ROWS rows of each) as DIR/W.npy, DIR/C.npy, the sampled row ids as "
+                         "DIR/rows.npy")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0, help="--full, N=1")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--seed", type=int, default=20251015)
     ap.add_argument("--semantics", default="cpp", choices=["cpp", "go"],
                     help="update rule: the C++ reference's (default) or the Go tree's (pkg/pronet)")
     ap.add_argument("--pmc", default="auto", choices=["auto", "off"],
-                    help="N=1: measure roofline.traffic with rocprofv3 --pmc in child runs of this config "
+                    help="--full, N=1: measure roofline.traffic with rocprofv3 --pmc in child runs of this config "
                          "before the timed run (off: the committed profiles/pmc_traffic.json)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -110,6 +126,10 @@ def parse():
     # while the adaptive scales assume one: not a valid combination
     if a.sync_every > 1 and a.exchanges_per_step > 1:
         ap.error("--sync-every > 1 needs --exchanges-per-step 1")
+    if a.dump_outputs and a.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1 (it runs the last step again from the seeded tables)")
+    if a.dump_outputs and a.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
     return a
 
 
@@ -237,6 +257,31 @@ def cpu_baseline(V, src, dst, w, dim, K, seconds, config):
                       "(every CPU this process can use: affinity capped by the cgroup CPU quota %s; %d CPUs on the "
                       "machine) in %.1f s, and %d samples on 1 thread in %.1f s"
                       % (dim, K, config, n_all, mine, quota, machine, t_all, n_one, t_one)}
+
+
+DUMP_ROWS = 1 << 16     # rows of each table in --dump-outputs (d=64: 16 MiB per table)
+
+
+def dump_outputs(pn, V, path, seed):
+    """--dump-outputs: the W (vertex) and C (context) tables as they stand
+    (main: after the last timed step run once more from the seeded initial
+    tables), as float32 .npy files.
+    Of tables of more than DUMP_ROWS rows, DUMP_ROWS rows drawn without
+    replacement by `seed` (vertex ids are randomly permuted, so hubs and cold
+    rows both fall in), the same ids in every run of the same arguments;
+    rows.npy holds them in ascending order (float64: ids are exact below 2^53).
+    Fewer rows when d > 64, so that the three files stay under 48 MiB."""
+    n = min(DUMP_ROWS, (48 << 20) // (2 * 4 * pn.dim + 8))
+    if V <= n:
+        rows = np.arange(V, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(seed).choice(V, n, replace=False)).astype(np.int64)
+    os.makedirs(path, exist_ok=True)
+    for name, which in (("W", 0), ("C", 1)):
+        t = pn.get_rows(which, rows)
+        assert np.isfinite(t).all(), "non-finite embeddings"
+        np.save(os.path.join(path, name + ".npy"), t)
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
 
 
 def graph_file(config):
@@ -375,7 +420,7 @@ def main():
     pmc_live, pmc_note = None, "off"
     # (not when this run is itself under a profiler: no nested rocprofv3)
     profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-    if world == 1 and not args.pmc_child and args.pmc == "auto" and not profiled:
+    if args.full and world == 1 and not args.pmc_child and args.pmc == "auto" and not profiled:
         pmc_live, pmc_note = pmc_traffic_live(args)
         print("[bench] pmc: %s" % (pmc_note if pmc_live is None else
                                    {k: round(v / args.samples, 1) for k, v in pmc_live.items()}),
@@ -566,13 +611,32 @@ def main():
             traffic_upd = p.get("hbm_bytes_per_launch")
             traffic_src = ("profiles/pmc_traffic.json: rocprofv3 --pmc of this config (%s)%s"
                            % (p.get("round", ""), "" if pmc_note == "off" else "; live measurement: " + pmc_note))
-    copy_peak = pn.copy_bandwidth(4 << 30, 5) if rank == 0 else 0.0   # membw.hip float4 copy
-    Wt = pn.get_table(0)
-    assert np.isfinite(Wt).all(), "non-finite embeddings"
+    copy_peak = None
+    if args.full:
+        copy_peak = pn.copy_bandwidth(4 << 30, 5) if rank == 0 else 0.0   # membw.hip float4 copy
+        Wt = pn.get_table(0)
+        assert np.isfinite(Wt).all(), "non-finite embeddings"
+    if args.dump_outputs:
+        # the tables after the timed steps are no function of the arguments:
+        # the hybrid scatter's plain stores lose colliding updates of the rows
+        # just under the hot threshold (which ones, no two runs share), and
+        # every later step reads the result.  What is written is the last
+        # timed step once more -- the same call, kernel, samples and learning
+        # rate -- from the seeded initial tables and with the hot threshold at
+        # 0, where every row is added atomically or through the LDS combine
+        # and no update is lost: what is left from run to run is the order of
+        # the float adds
+        torch.cuda.synchronize()
+        pn.set_hot_threshold(0.0)
+        pn.init_table_uniform(0, args.seed)
+        pn.zero_table(1)
+        step(args.warmup + args.steps - 1)
+        torch.cuda.synchronize()
+        dump_outputs(pn, V, args.dump_outputs, args.seed)
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.cpu_baseline_seconds > 0:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_baseline_seconds > 0:
             cpu = cpu_baseline(V, src, dst, w, args.dim, K, args.cpu_baseline_seconds, args.config)
         out = {
             "metric": "M edge-updates/sec (d=64, neg=5)",
@@ -615,11 +679,12 @@ def main():
                          "bytes_per_update_read": R, "bytes_per_update_write": Wb,
                          "ms_per_step": round(step_s * 1e3, 3),
                          "traffic_per_algorithmic": (round(traffic / ((R + Wb) * S), 3) if traffic else None),
-                         "measured_peak": {"copy_GBs": round(copy_peak, 1),
-                                           "frac": round((R + Wb) * S / step_s / 1e9 / copy_peak, 4),
-                                           "note": "the path's algorithmic read+write bytes per second over the "
-                                                   "library's float4 device copy (membw.hip, 4 GiB, best of "
-                                                   "default / non-temporal policy and 4 / 8 blocks per CU)"},
+                         "measured_peak": None if copy_peak is None else {
+                             "copy_GBs": round(copy_peak, 1),
+                             "frac": round((R + Wb) * S / step_s / 1e9 / copy_peak, 4),
+                             "note": "the path's algorithmic read+write bytes per second over the "
+                                     "library's float4 device copy (membw.hip, 4 GiB, best of "
+                                     "default / non-temporal policy and 4 / 8 blocks per CU)"},
                          "kernel": {"name": ("block cells: block_draw_kernel + edge_train_kernel per cell"
                                              if blocks else "edge_train_kernel (gather/update/scatter)"),
                                     "achieved": round(achieved, 1), "frac": round(achieved / HBM_PEAK_GBS, 4),

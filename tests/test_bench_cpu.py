@@ -34,6 +34,52 @@ def test_pmc_per_launch_ignores_other_counters(tmp_path):
     assert got["draw_kernel"] == (16 + 12) / 2 * 1024 * bench.FETCH_CORRECTION
 
 
+class _FakeTables:
+    """get_rows of two tables whose row i holds i (W) or -i (C)."""
+    dim = 4
+
+    def get_rows(self, which, ids):
+        import numpy as np
+        return (np.asarray(ids, np.float32)[:, None] * (1 - 2 * which)).repeat(self.dim, 1)
+
+
+def test_dump_outputs_row_sample(tmp_path):
+    """--dump-outputs: the same seeded rows in every run, ascending and
+    distinct, DUMP_ROWS of a larger table and all of a smaller one; W / C as
+    float32 rows of those ids, rows.npy as float64."""
+    import numpy as np
+    V = 3 * bench.DUMP_ROWS + 17
+    a, b, c = str(tmp_path / "a"), str(tmp_path / "b"), str(tmp_path / "c")
+    bench.dump_outputs(_FakeTables(), V, a, 5)
+    bench.dump_outputs(_FakeTables(), V, b, 5)
+    bench.dump_outputs(_FakeTables(), 1000, c, 5)
+    ra, rb, rc = (np.load(os.path.join(d, "rows.npy")) for d in (a, b, c))
+    assert ra.dtype == np.float64 and ra.shape == (bench.DUMP_ROWS,) and np.array_equal(ra, rb)
+    assert (np.diff(ra) > 0).all() and ra[0] >= 0 and ra[-1] < V and np.array_equal(ra, np.floor(ra))
+    assert np.array_equal(rc, np.arange(1000.0))
+    assert 2 * bench.DUMP_ROWS * 64 * 4 + 8 * bench.DUMP_ROWS <= 64 << 20     # d=64: under 64 MB in all
+    W, Ct = np.load(os.path.join(a, "W.npy")), np.load(os.path.join(a, "C.npy"))
+    assert W.dtype == np.float32 and W.shape == (bench.DUMP_ROWS, 4)
+    assert np.array_equal(W[:, 0], ra.astype(np.float32)) and np.array_equal(Ct, -W)
+    assert sorted(os.listdir(a)) == ["C.npy", "W.npy", "rows.npy"]
+
+
+def test_plain_run_defaults():
+    """--full and --dump-outputs are off unless asked for."""
+    import unittest.mock as mock
+    with mock.patch.object(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]):
+        a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    with mock.patch.object(sys, "argv", ["bench.py", "--full", "--dump-outputs", "x"]):
+        a = bench.parse()
+    assert a.full is True and a.dump_outputs == "x"
+    # the dump replays the last step on one GPU's tables: refused at N > 1
+    import pytest
+    with mock.patch.object(sys, "argv", ["bench.py", "--gpus", "2", "--dump-outputs", "x"]):
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
 def test_samples_to_loss_interpolation(tmp_path):
     """tools/samples_to_loss.py: the N-replica total that reaches one
     replica's loss, by log-linear interpolation, and the effective speed-up

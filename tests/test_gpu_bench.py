@@ -41,12 +41,44 @@ def _check_contract(d, n, schedule="blocks"):
 
 
 def test_bench_json_line_n1():
-    p = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline"] + SMALL, cwd=ROOT,
+    """--full (here without its CPU baseline and live PMC legs): the copy
+    bandwidth and the whole-table finite check run too."""
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline"] + SMALL, cwd=ROOT,
                        capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _json_line(p.stdout)
     _check_contract(d, 1)
     assert d["cpu_baseline"] is None and d["config"]["sync"] == "none"
+    mp = d["roofline"]["measured_peak"]
+    assert mp["copy_GBs"] > 0 and mp["frac"] > 0
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) measures nothing of its own beyond the steps
+    -- no CPU baseline, no copy bandwidth, the committed traffic or none --
+    and --dump-outputs writes the W and C tables the last step leaves when
+    run once more from the seeded tables: the small config has 100000 rows,
+    so the seeded sample of bench.DUMP_ROWS rows, float32, finite, trained
+    (C starts at zero), under 64 MB in all."""
+    import numpy as np
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(out)] + SMALL[:-2],
+                       cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _json_line(p.stdout)
+    _check_contract(d, 1)
+    assert d["cpu_baseline"] is None and d["roofline"]["measured_peak"] is None
+    assert "pmc:" not in p.stderr      # no live rocprofv3 child runs
+    assert sorted(f.name for f in out.iterdir()) == ["C.npy", "W.npy", "rows.npy"]
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    rows = np.load(out / "rows.npy")
+    n = min(65536, d["config"]["vertices"])
+    assert rows.dtype == np.float64 and rows.shape == (n,)
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < d["config"]["vertices"]
+    for name in ("W", "C"):
+        t = np.load(out / (name + ".npy"))
+        assert t.dtype == np.float32 and t.shape == (n, 64) and np.isfinite(t).all()
+        assert np.count_nonzero(np.abs(t).sum(1)) > n // 2
 
 
 @pytest.mark.parametrize("schedule", ["blocks", "replicas"])
@@ -56,7 +88,7 @@ def test_bench_json_line_n2_gloo_ranks(schedule):
         port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
+                        "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--full",
                         "--dist-backend", "gloo", "--schedule", schedule] + SMALL, cwd=ROOT, capture_output=True, text=True, timeout=300,
                        env=env)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -75,7 +107,7 @@ def test_bench_gpus_flag_starts_the_ranks():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo"] + SMALL, cwd=ROOT,
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--dist-backend", "gloo"] + SMALL, cwd=ROOT,
                        capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _json_line(p.stdout)

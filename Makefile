@@ -15,7 +15,7 @@ LIB      ?= smore_amd/lib/libsmore_hip.so
 BIN      := smore_amd/bin
 # kernels depend on the device headers only; host objects on the host headers
 DEV_HDRS := $(SRC)/device_common.h $(SRC)/train_kernels.h $(SRC)/edge_kernels.h $(SRC)/edge_inst.h
-HOST_HDRS := $(SRC)/host_graph.h $(SRC)/ctx.h $(SRC)/train_kernels.h $(SRC)/device_common.h $(SRC)/go_walks.h \
+HOST_HDRS := $(SRC)/host_graph.h $(SRC)/ctx.h $(SRC)/train_host.h $(SRC)/train_kernels.h $(SRC)/device_common.h $(SRC)/go_walks.h \
              $(SRC)/hot_exchange.h $(SRC)/comm_watch.h include/smore_hip.h
 
 .PHONY: all lib cli goshape oracle ref clean
@@ -23,7 +23,7 @@ all: lib cli goshape
 
 lib: $(LIB)
 
-HOST_SRCS := host_graph loader capi exchange graphgen blocks
+HOST_SRCS := host_graph loader capi hot_maps train pairs_rows exchange graphgen blocks
 $(OBJ)/%.o: $(SRC)/%.cpp $(HOST_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(CXXFLAGS) -c -o $@ $<

@@ -503,7 +503,7 @@ func (pn *ProNet) pairSession() *pairSession {
 // goroutines do NOT take turns on a lock: each calls
 // smore_train_pairs_rows_mt, which combines every batch queued while the
 // device is busy into one call (the union of their rows up once, the batches
-// in queue order, the union back; capi.cpp PairCombiner), so the reference's
+// in queue order, the union back; pairs_rows.cpp PairCombiner), so the reference's
 // `workers` goroutines share one synchronisation instead of paying one each.
 // UpdatePairs has no error path (the reference panics on a bad index):
 // failures panic.

@@ -25,7 +25,7 @@
 #include <numeric>
 #include <thread>
 
-#include "ctx.h"
+#include "train_host.h"
 
 using namespace smore_host;
 
@@ -64,22 +64,17 @@ uint32_t prob_thr(double p) {
 // the resident sample groups of this context's update launches (the hot
 // tags' M): the same grid the training calls use
 int64_t resident_groups(smore_ctx* c, bool walk, int K, int mode) {
-    EdgeArgs a{};
-    a.g = dev_graph(c);
-    a.dpad = c->dpad;
-    a.K = K;
-    a.model = SMORE_LINE2;
-    a.mode = mode;
+    EdgeArgs a = record_args(c, SMORE_LINE2, K, mode);
     a.count = (uint64_t)1 << 30;
     a.alpha_rec = walk ? 1 : 0;
     a.sh_rows = mode == SMORE_HYBRID ? std::min(c->sh_max, sh_rows_max(c->dpad)) : 0;
-    return (int64_t)launch_grid(c, a) * (256 / lanes_of(c->dpad));
+    return (int64_t)edge_grid(c, a) * (256 / lanes_of(c->dpad));
 }
 
 // per-block write-combined rows: the hottest hot C rows of each block under
 // its cell's C-row law (pcb, flags hcb; entry i of block k is row cb[k] + i,
 // or hub slot V + i - rows past the block's rows), with the edge rule's
-// staleness bound and a two-tier drain (capi build_hot_maps)
+// staleness bound and a two-tier drain (hot_maps.cpp build_hot_maps)
 // Walk cells add their part's hottest W rows (key v | SH_WKEY, rate ps(v) N
 // per record: wcand): the pair kernel keeps a run's W row in registers and
 // flushed it atomically at the run's end, so C5's hub centre -- ~1 record
@@ -99,10 +94,10 @@ void block_sh_sets(smore_ctx* c, bool walk, bool on, int64_t Mg, const std::vect
     B.sh_lvl.assign((size_t)B.nb, std::array<int, 8>{});
     hash.assign((size_t)B.nb * SH_HASH, make_int2(-1, -1));
     ids.assign((size_t)B.nb * B.sh_cap, -1);
-    const int flush_cap = c->sh_flush > 0 ? c->sh_flush : sh_flush_max(walk);
+    const int flush_cap = c->sh_flush > 0 ? c->sh_flush : (walk ? PAIR_FLUSH_MAX : EDGE_FLUSH_MAX);
     B.sh_flush = flush_cap;
     if (cap == 0) return;
-    const double M = (double)Mg, stale = sh_stale_max(walk);
+    const double M = (double)Mg, stale = sh_stale(walk), budget = cell_budget(walk);
     const bool two_tier = c->sh_flush <= 0;
     for (int k = 0; k < B.nb; ++k) {
         // A cell concentrates its samples on 1/nb of the C rows, so a hub row
@@ -117,12 +112,12 @@ void block_sh_sets(smore_ctx* c, bool walk, bool on, int64_t Mg, const std::vect
         for (size_t i = 0; i < pcb[k].size(); ++i) {
             if (!hcb[k][i]) continue;
             const double p = pcb[k][i];
-            const double f = two_tier ? (double)sh_slot_interval(M * p, flush_cap, walk) : (double)flush_cap;
+            const double f = two_tier ? (double)slot_interval(M * p, flush_cap, budget) : (double)flush_cap;
             const int64_t id = (int64_t)i < rows ? B.cb[k] + (int64_t)i : V + ((int64_t)i - rows);
             if (M * p * f <= stale) r.push_back({p, (int32_t)id});
         }
         for (const auto& x : wcand) {
-            const double f = two_tier ? (double)sh_slot_interval(M * x.first, flush_cap, walk) : (double)flush_cap;
+            const double f = two_tier ? (double)slot_interval(M * x.first, flush_cap, budget) : (double)flush_cap;
             if (M * x.first * f <= stale) r.push_back(x);
         }
         const int64_t n = std::min<int64_t>(cap, (int64_t)r.size());
@@ -140,7 +135,7 @@ void block_sh_sets(smore_ctx* c, bool walk, bool on, int64_t Mg, const std::vect
         B.sh_n[k] = (int)n;
         if (two_tier && n > 0) {
             int lv[8];
-            sh_slot_levels(Mg, flush_cap, walk, r.data(), n, lv);
+            sh_levels(Mg, flush_cap, budget, r.data(), n, lv);
             std::copy(lv, lv + 8, B.sh_lvl[k].begin());
         }
         if (getenv("SMORE_SH_DEBUG")) {
@@ -194,18 +189,8 @@ int64_t hub_count(const smore_ctx* c, int64_t V, int nb, bool walk) {
 // the update-kernel arguments shared by a context's cell launches
 EdgeArgs cell_args(smore_ctx* c, int k, bool walk) {
     const auto& B = c->blk;
-    EdgeArgs a{};
-    a.g = dev_graph(c);
-    a.sig = c->d_sig;
-    a.W = c->d_table[0];
-    a.C = c->d_table[1];
-    a.skipped = c->d_skipped;
-    a.dpad = c->dpad;
-    a.K = B.K;
-    a.model = SMORE_LINE2;
-    a.mode = B.mode;
+    EdgeArgs a = record_args(c, SMORE_LINE2, B.K, B.mode);
     a.alpha_rec = walk ? 1 : 0;
-    a.work = c->d_work;
     const bool on = B.mode == SMORE_HYBRID && B.sh_n[k] > 0;
     a.sh_rows = on ? B.sh_n[k] : 0;
     a.sh_hash = B.d_sh_hash + (size_t)k * SH_HASH;
@@ -242,10 +227,10 @@ EdgeArgs cell_args(smore_ctx* c, int k, bool walk) {
 // flight (C5 DeepWalk, 8 GPUs) diverges whether the row is atomic or
 // write-combined.
 int cell_grid(smore_ctx* c, const EdgeArgs& a, int k) {
-    int grid = launch_grid(c, a);
+    int grid = edge_grid(c, a);
     const auto& B = c->blk;
     if (a.mode == SMORE_SERIAL || (size_t)k >= B.pmax_c.size()) return grid;
-    // LINE-2 cells: the one-GPU launch's Hogwild concurrency cap (capi
+    // LINE-2 cells: the one-GPU launch's Hogwild concurrency cap (train.cpp
     // edge_grid: at most V / 16 resident sample groups) applied to the rows a
     // cell updates -- its block's C rows and the hub slots -- so a small
     // graph's cells (C2 at 8 GPUs: 62k rows per block) keep the one-GPU ratio
@@ -256,7 +241,7 @@ int cell_grid(smore_ctx* c, const EdgeArgs& a, int k) {
         const int64_t cap = std::max<int64_t>(8, (rows / 16 + gpb - 1) / gpb);
         if (cap < grid) grid = (int)cap;
     }
-    double cap = cell_rate_default(a.alpha_rec == 1);
+    double cap = a.alpha_rec == 1 ? CELL_RATE_PAIRS : CELL_RATE_EDGES;
     if (const char* e = getenv("SMORE_CELL_RATE")) cap = atof(e);
     // which side's hub sets the cap: both (default), SMORE_CELL_SIDE=c or w
     const char* side = getenv("SMORE_CELL_SIDE");
@@ -267,15 +252,6 @@ int cell_grid(smore_ctx* c, const EdgeArgs& a, int k) {
     const double groups = cap / pmax;
     const int g = std::max(8, (int)(groups / gpb) / 8 * 8);   // whole rounds of the 8 XCDs
     return std::min(grid, g);
-}
-
-int grow_events(smore_ctx* c, std::vector<hipEvent_t>& v, size_t n) {
-    while (v.size() < n) {
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreate(&e));
-        v.push_back(e);
-    }
-    return SMORE_OK;
 }
 
 }  // namespace
@@ -341,6 +317,8 @@ int block_walks_gen(smore_ctx* c, int rule, uint64_t walk_begin, uint64_t walk_e
     if (walk_begin >= walk_end) return SMORE_OK;
     const uint64_t nw = walk_end - walk_begin;
     if (nw > WALK_ROUND_MAX) return fail(c, SMORE_EINVAL, "a block round holds at most 2^20 walks");
+    if (gen_lo < walk_begin || gen_hi > walk_end || gen_lo > gen_hi)
+        return fail(c, SMORE_EINVAL, "walk generation range outside the round");
     if (order) {
         if (walk_begin < order_base) return fail(c, SMORE_EINVAL, "walk order slice does not cover the range");
         order -= order_base;
@@ -351,32 +329,16 @@ int block_walks_gen(smore_ctx* c, int rule, uint64_t walk_begin, uint64_t walk_e
     // the walk ids' tags: the scaled hot maps (a no-op when current)
     if (mode == SMORE_HYBRID) {
         const int64_t M = resident_groups(c, true, K, mode);
-        if ((rc = hot_maps(c, SMORE_LINE2, K, M, true, (double)B.n, (double)B.nb))) return rc;
+        if ((rc = build_hot_maps(c, SMORE_LINE2, K, M, HOT_TAU_WALK, PAIR_FLUSH_MAX, (double)B.n, (double)B.nb))) return rc;
     }
     if (order) {
-        if (c->order_cap < nw) {
-            dfree(c->d_order);
-            c->order_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->d_order, nw * sizeof(int64_t)));
-            c->order_cap = nw;
-        }
+        if ((rc = ensure_cap(c, c->d_order, c->order_cap, (size_t)nw))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->d_order, order + walk_begin, nw * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     }
     const int RW = rec_width(kmax_of(K));
     const uint64_t pb = std::max<uint64_t>(1, pair_bound(walk_steps, window, rule, window_min));
-    const size_t need = nw * (size_t)(walk_steps + 1);
-    if (c->walk_buf_n < need) {
-        dfree(c->d_walks);
-        c->walk_buf_n = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_walks, need * sizeof(int32_t)));
-        c->walk_buf_n = need;
-    }
-    if (c->walk_lens_n < nw) {
-        dfree(c->d_lens);
-        c->walk_lens_n = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_lens, nw * sizeof(int32_t)));
-        c->walk_lens_n = nw;
-    }
+    if ((rc = ensure_cap(c, c->d_walks, c->walk_buf_n, (size_t)nw * (size_t)(walk_steps + 1)))) return rc;
+    if ((rc = ensure_cap(c, c->d_lens, c->walk_lens_n, (size_t)nw))) return rc;
     const size_t ncount = (size_t)B.nb * nw + 1;
     if (B.count_cap < ncount) {
         dfree(B.d_count);
@@ -386,12 +348,7 @@ int block_walks_gen(smore_ctx* c, int rule, uint64_t walk_begin, uint64_t walk_e
         HIPCHK(c, hipMalloc((void**)&B.d_off, ncount * sizeof(uint64_t)));
         B.count_cap = ncount;
     }
-    if (c->rec_cap < nw * pb * RW) {
-        dfree(c->d_rec);
-        c->rec_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_rec, nw * pb * RW * sizeof(int32_t)));
-        c->rec_cap = nw * pb * RW;
-    }
+    if ((rc = ensure_cap(c, c->d_rec, c->rec_cap, (size_t)(nw * pb * RW)))) return rc;
     WalkArgs w;
     w.order = order ? c->d_order : nullptr;
     w.order_base = walk_begin;
@@ -422,8 +379,6 @@ int block_walks_gen(smore_ctx* c, int rule, uint64_t walk_begin, uint64_t walk_e
     B.wpairs = pb;
     B.walks = nw;
     B.rec_bound = nw * pb;
-    if (gen_lo < walk_begin || gen_hi > walk_end || gen_lo > gen_hi)
-        return fail(c, SMORE_EINVAL, "walk generation range outside the round");
     if (gen_hi > gen_lo) {   // this context's share of the round's walks
         WalkArgs wg = w;
         const uint64_t o = gen_lo - walk_begin;
@@ -527,11 +482,11 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
         }
         B.H = H;
     }
-    part_bounds(ps, nparts, B.wb);
+    source_bounds(ps, nparts, B.wb);
     {   // C blocks of equal NON-hub negative mass (the hubs are in every block)
         std::vector<double> pcut = pn;
         for (int32_t x : B.hubs) pcut[x] = 0.0;
-        part_bounds(pcut, nb, B.cb);
+        source_bounds(pcut, nb, B.cb);
     }
     for (int p = 0; p < nparts; ++p)
         if (B.wb[p + 1] <= B.wb[p]) return fail(c, SMORE_EINVAL, "block schedule: an empty W part");
@@ -553,7 +508,7 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
         for (int k = 0; k < nb; ++k) B.nmass[k] = tot > 0 ? nraw[k] / tot : 1.0 / nb;
     }
     // each part's share of the source law: a round's samples are split over
-    // the replicas by it (part_bounds only makes the parts roughly equal; a
+    // the replicas by it (source_bounds only makes the parts roughly equal; a
     // hub above 1/N of the mass puts a part far off)
     {
         B.part_mass.assign((size_t)nparts, 0.0);
@@ -570,7 +525,7 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
     // law -- so a row is atomic iff M * p > tau in the launch that trains it
     // (a scaled global law misses the sources whose contexts crowd one block:
     // up to nb times hotter in that cell).  Walks: the scaled global law
-    // (capi build_hot_maps), whose tags the walk ids carry.
+    // (hot_maps.cpp build_hot_maps), whose tags the walk ids carry.
     const bool hyb = mode == SMORE_HYBRID;
     int64_t M = 0;
     double tau = 0.0;
@@ -585,9 +540,9 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
         // block at 4 parts -- 1.048x, so graphs under 4M vertices keep 0.3;
         // DESIGN.md 10.6)
         const bool t06 = !walk && nparts >= 3 && nparts <= 4 && V >= ((int64_t)1 << 22);
-        const double tcell = t06 ? 0.6 : hot_tau_cell_default(walk);
+        const double tcell = t06 ? 0.6 : (walk ? HOT_TAU_WALK : HOT_TAU_CELL);
         tau = c->hot_tau >= 0 ? c->hot_tau : small ? 0.0 : tcell;
-        if (walk && (rc = hot_maps(c, SMORE_LINE2, K, M, true, (double)nparts, (double)nb))) return rc;
+        if (walk && (rc = build_hot_maps(c, SMORE_LINE2, K, M, HOT_TAU_WALK, PAIR_FLUSH_MAX, (double)nparts, (double)nb))) return rc;
     }
     const int T = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), (unsigned)nb);
     auto par_blocks = [&](auto&& f) {
@@ -714,7 +669,7 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
             auto& pcx = pcb[k];
             pcx.assign((size_t)(n + H), 0.0);
             hcb[k].assign((size_t)(n + H), 0);
-            if (walk) {   // capi build_hot_maps' scaled law (hot_pc); the hub slots at their global rate
+            if (walk) {   // hot_maps.cpp build_hot_maps' scaled law (hot_pc); the hub slots at their global rate
                 double mx = 0.0;
                 for (int64_t i = 0; i < n; ++i) {
                     pcx[i] = is_hub(lo + i) ? 0.0 : (pc[lo + i] + K * pn[lo + i]) * nb;
@@ -996,12 +951,7 @@ int smore_block_train_edges_async(smore_ctx* c, int block, uint64_t begin, uint6
     const uint64_t chunk_max = mode == SMORE_SERIAL ? ((uint64_t)1 << 30) / (uint64_t)RW : (uint64_t)1 << 27;
     const uint64_t chunk = std::min<uint64_t>(count, chunk_max);
     const int nch = (int)((count + chunk - 1) / chunk);
-    if (c->rec_cap < chunk * RW) {
-        dfree(c->d_rec);
-        c->rec_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_rec, chunk * RW * sizeof(int32_t)));
-        c->rec_cap = chunk * RW;
-    }
+    if ((rc = ensure_cap(c, c->d_rec, c->rec_cap, (size_t)(chunk * RW)))) return rc;
     if ((rc = grow_events(c, c->phase_ev, 2 * (size_t)nch + 1))) return rc;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     HIPCHK(c, hipEventRecord(c->phase_ev[0], c->stream));
@@ -1018,11 +968,7 @@ int smore_block_train_edges_async(smore_ctx* c, int block, uint64_t begin, uint6
         HIPCHK(c, launch_edge_train(ak, grid, c->stream));
         HIPCHK(c, hipEventRecord(c->phase_ev[2 * k + 2], c->stream));
     }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
-    c->last_mode = mode;
-    c->phase_n = nch;
-    return SMORE_OK;
+    return finish_timed(c, mode, nch);
 }
 
 int smore_block_sample_edges(smore_ctx* c, int block, uint64_t seed, uint64_t begin, uint64_t count, int K,

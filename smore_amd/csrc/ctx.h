@@ -1,6 +1,8 @@
 // ctx.h -- the library context (one GPU's graph, tables and buffers) and the
 // host-side helpers shared by the C ABI translation units (capi.cpp,
-// exchange.cpp).  Internal: not part of the installed interface.
+// hot_maps.cpp, train.cpp, pairs_rows.cpp, blocks.cpp, exchange.cpp; what only
+// the training paths share is in train_host.h).  Internal: not part of the
+// installed interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,7 +58,7 @@ struct smore_ctx {
     bool timed = false;
     int last_mode = -1;                 // scatter (SMORE_* mode) the last timed training call ran
     // smore_train_pairs_rows_mt: the combining queue of concurrent callers
-    // (capi.cpp PairCombiner; created on first use)
+    // (pairs_rows.cpp PairCombiner; created on first use)
     std::shared_ptr<struct PairCombiner> pair_comb;
     int64_t blk_hubs = -1;              // hub C rows of the block schedule (smore_block_set_hubs; -1 automatic)
     int64_t c_slots = 0;                // rows after V in the C table (the block schedule's hub slots)
@@ -93,7 +95,7 @@ struct smore_ctx {
     int2* d_sh_hash = nullptr;
     int32_t* d_sh_ids = nullptr;
     int sh_rows = 0;
-    int sh_max = 128, sh_flush = 0;      // flush 0: automatic drain interval (capi build_hot_maps)
+    int sh_max = 128, sh_flush = 0;      // flush 0: automatic drain interval (hot_maps.cpp build_hot_maps)
     int sh_flush_eff = 32;               // the interval of the last hybrid launch
     int sh_flush_w_eff = 0;              // its W-key slots' own interval (0: none)
     int sh_lvl_eff[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // its per-slot drain levels (EdgeArgs::sh_lvl)
@@ -159,12 +161,12 @@ struct smore_ctx {
     std::string census_key;             // what the group driver censused (exchange.cpp)
     // caller-supplied pairs (smore_train_pairs): a chunk of (v, c) on the device
     int32_t* d_pairs = nullptr;
-    size_t pairs_cap = 0;               // pairs
+    size_t pairs_cap = 0;               // int32 words (two per pair)
     // row transfers (smore_set_rows / smore_get_rows): ids and dense rows
     int32_t* d_io_ids[2] = {nullptr, nullptr};   // [W, C] of smore_train_pairs_rows
     float* d_io_rows[2] = {nullptr, nullptr};
     size_t io_cap[2] = {0, 0};          // rows
-    // the last hybrid hot maps' host side (capi build_hot_maps): row flags and
+    // the last hybrid hot maps' host side (hot_maps.cpp build_hot_maps): row flags and
     // the C-row touch law they were made from, for the block tables' own tags
     std::vector<uint8_t> hot_c, hot_w;
     std::vector<double> hot_pc;
@@ -370,17 +372,6 @@ inline DevGraph dev_graph(const smore_ctx* c) {
     return d;
 }
 
-// capi.cpp helpers shared with blocks.cpp
-void part_bounds(const std::vector<double>& ps, int n, std::vector<int64_t>& bound);
-int hot_maps(smore_ctx* c, int model, int K, int64_t M, bool walk, double w_scale, double c_scale);
-int launch_grid(smore_ctx* c, const EdgeArgs& a);
-int sh_flush_max(bool walk);
-int sh_slot_interval(double Mp, int cap, bool walk);
-void sh_slot_levels(int64_t M, int cap, bool walk, const std::pair<double, int32_t>* r, int64_t n, int (&lvl)[8]);
-double hot_tau_default(bool walk);
-double hot_tau_cell_default(bool walk);
-double cell_rate_default(bool walk);
-double sh_stale_max(bool walk);
 inline float* table_ptr(smore_ctx* c, int which) {
     if (which < 0 || which > 1) return nullptr;
     return c->d_table[which];

@@ -1,6 +1,6 @@
 // go_walks.h -- Go CTDNE's temporal walk (internal/models/ctdne/ctdne.go,
 // pkg/temporal/temporal_graph.go): device arrays and launchers shared by the
-// C ABI (capi.cpp) and train_go.hip.
+// C ABI (train.cpp) and train_go.hip.
 #pragma once
 #include "train_kernels.h"
 

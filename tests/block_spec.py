@@ -4,7 +4,7 @@ train_blocks.hip, never the product).
 
 A context that is part r of N (smore_block_setup) holds:
   * W part bounds: contiguous ids of equal source mass (the midpoint rule of
-    capi.cpp source_bounds) under the source law SourceSample draws
+    hot_maps.cpp source_bounds) under the source law SourceSample draws
     (src/proNet.cpp:647-657);
   * 2N C block bounds: the same rule over NegativeSample's law (:623-633);
   * per C block k, the negative law restricted to the block, as a Go-rule

@@ -256,19 +256,27 @@ def test_block_group_serial_equals_schedule(smore, graph, n, hubs):
     g.close()
 
 
-def test_block_walk_rounds_cover_the_pairs(smore, graph):
-    """Every part's pair records, over all blocks, are the one-context
-    records: for DeepWalk the per-walk pair counts of the oracle's SkipGrams
-    (the window draws are shared), for Walklets the clamped ranges."""
+@pytest.fixture(scope="module")
+def round_pairs(smore, graph):
+    """The walk order and the pair total of one context's DeepWalk round
+    [0, 700) on pl1k (2 walks per vertex, 20 steps, window 4, K 5), by census."""
     K = 5
-    V = graph.V
-    order = orc.deepwalk_order(V, 2, 0)
+    order = orc.deepwalk_order(graph.V, 2, 0)
     one = _ctx(smore)
     one.census_begin()
     one.train_deepwalk(0, 700, 2, 20, 4, K, 0.025, SEED, order, "atomic")
     one.census_end(1.0)
     total_pairs = int(round(one.row_rates("census", K, 0).sum()))
     one.close()
+    return order, total_pairs
+
+
+def test_block_walk_rounds_cover_the_pairs(smore, graph, round_pairs):
+    """Every part's pair records, over all blocks, are the one-context
+    records: for DeepWalk the per-walk pair counts of the oracle's SkipGrams
+    (the window draws are shared), for Walklets the clamped ranges."""
+    K = 5
+    order, total_pairs = round_pairs
     for n in (2, 4):
         got = 0
         for r in range(n):
@@ -278,6 +286,27 @@ def test_block_walk_rounds_cover_the_pairs(smore, graph):
             got += sum(pn.block_walk_records(b) for b in range(2 * n))
             pn.close()
         assert got == total_pairs, (n, got, total_pairs)
+
+
+def test_block_walks_generate_rejected_range_prepares_nothing(smore, graph, round_pairs):
+    """A generation range that leaves the round is refused before the round
+    is prepared: every bucket then reports 0 records (no prepared round, so
+    nothing is read from the device), and a valid round on the same context
+    still holds exactly the one-context pairs."""
+    K, n = 5, 2
+    order, total_pairs = round_pairs
+    got = 0
+    for r in range(n):
+        pn = _ctx(smore)
+        pn.block_setup("census", n, r, K, "atomic")
+        with pytest.raises(smore._lib.SmoreError,
+                           match=r"block_walks_generate failed \(status 1\): walk generation range outside the round"):
+            pn.block_walks_generate(0, 700, 0, 701, 2, 20, 4, K, 0.025, SEED, order, "atomic")
+        assert [pn.block_walk_records(b) for b in range(2 * n)] == [0] * (2 * n)
+        pn.block_prepare_walks(0, 700, 2, 20, 4, K, 0.025, SEED, order, "atomic")
+        got += sum(pn.block_walk_records(b) for b in range(2 * n))
+        pn.close()
+    assert got == total_pairs, (got, total_pairs)
 
 
 @pytest.mark.parametrize("n,rule,steps,window,K", [(2, "deepwalk", 20, 4, 5), (3, "deepwalk", 100, 10, 5),

@@ -16,14 +16,14 @@ BIN      := smore_amd/bin
 # kernels depend on the device headers only; host objects on the host headers
 DEV_HDRS := $(SRC)/device_common.h $(SRC)/train_kernels.h $(SRC)/edge_kernels.h $(SRC)/edge_inst.h
 HOST_HDRS := $(SRC)/host_graph.h $(SRC)/ctx.h $(SRC)/train_host.h $(SRC)/train_kernels.h $(SRC)/device_common.h $(SRC)/go_walks.h \
-             $(SRC)/hot_exchange.h $(SRC)/comm_watch.h include/smore_hip.h
+             $(SRC)/hot_exchange.h $(SRC)/comm_watch.h $(SRC)/group.h $(SRC)/block_plan.h include/smore_hip.h
 
-.PHONY: all lib cli goshape oracle ref clean
-all: lib cli goshape
+.PHONY: all lib cli goshape plan_check oracle ref clean
+all: lib cli goshape plan_check
 
 lib: $(LIB)
 
-HOST_SRCS := host_graph loader capi hot_maps train pairs_rows exchange graphgen blocks
+HOST_SRCS := host_graph loader capi hot_maps train pairs_rows exchange group group_blocks graphgen blocks block_plan
 $(OBJ)/%.o: $(SRC)/%.cpp $(HOST_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
@@ -67,3 +67,10 @@ tests/c/go_shape: tests/c/go_shape.c include/smore_hip.h $(LIB)
 	gcc -std=c11 -O2 -Wall -Iinclude -o $@ $< -L$(dir $(LIB)) -lsmore_hip -Wl,-rpath,'$$ORIGIN/../../smore_amd/lib'
 tests/c/pairs_mt: tests/c/pairs_mt.c include/smore_hip.h $(LIB)
 	gcc -std=gnu11 -O2 -Wall -Iinclude -o $@ $< -L$(dir $(LIB)) -lsmore_hip -lpthread -Wl,-rpath,'$$ORIGIN/../../smore_amd/lib'
+
+# the block schedule's host-only plan (block_plan.cpp) as a CPU program that
+# writes its tables to files (tests/test_block_plan_cpu.py): plain g++, no ROCm
+plan_check: tests/c/block_plan_check
+tests/c/block_plan_check: tests/c/block_plan_check.cpp $(SRC)/block_plan.cpp $(SRC)/block_plan.h $(SRC)/host_graph.cpp \
+                          $(SRC)/loader.cpp $(SRC)/host_graph.h
+	g++ -std=c++17 -O2 -ffp-contract=off -Wall -o $@ $< $(SRC)/block_plan.cpp $(SRC)/host_graph.cpp $(SRC)/loader.cpp -lpthread

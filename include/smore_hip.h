@@ -276,7 +276,7 @@ int smore_row_rates(smore_ctx* ctx, int model, int K, int which, int64_t n, doub
  * SMORE_ESTATE while an exchange is in flight (call smore_exchange_end first). */
 int smore_exchange_set_adaptive(smore_ctx* ctx, int model, int K, double updates, double c0);
 
-/* ---- multi-GPU replicas over RCCL, in the library (smore_amd/csrc/exchange.cpp) ------
+/* ---- multi-GPU replicas over RCCL, in the library (smore_amd/csrc/exchange.cpp, group.cpp) --
  * replaces: the fan-out of one training run over the reference's workers
  * (LINE::Train `#pragma omp parallel for`, src/model/LINE.cpp:162; MF.cpp /
  * BPR.cpp / DeepWalk.cpp Train likewise; Go goroutines per worker,

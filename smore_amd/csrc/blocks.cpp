@@ -11,7 +11,7 @@
 // mass), and sub-round s trains cell (r, b = (2r + s) mod nb) on every GPU at
 // once -- disjoint W rows, disjoint C rows.  After a sub-round GPU r passes
 // block b to GPU r - 1, which trains it two sub-rounds later, so the transfer
-// has a whole sub-round to overlap (exchange.cpp group_rotate, dist.py
+// has a whole sub-round to overlap (group_blocks.cpp group_rotate, dist.py
 // BlockSync).  The samples of a cell follow the one-GPU law restricted to the
 // cell (train_blocks.hip); a call's samples are spread over the cells in
 // proportion to their mass, so an epoch (nb sub-rounds) draws the one-GPU
@@ -22,9 +22,8 @@
 // block's negative share over its sample share (cell_args, neg_law_on), and
 // an epoch's expected negative updates per row are NegativeSample's.
 #include <cmath>
-#include <numeric>
-#include <thread>
 
+#include "block_plan.h"
 #include "train_host.h"
 
 using namespace smore_host;
@@ -178,12 +177,44 @@ constexpr int64_t HUB_AUTO = 4096;
 // and the 29 % rotation stall disappear, 1.34 -> 2.32x predicted) with their
 // own exchange rule (c0 64, hub_c0: 1.026 times one GPU's held-out loss; c0
 // 2048: 1.11).
-int64_t hub_count(const smore_ctx* c, int64_t V, int nb, bool walk) {
-    (void)walk;
+int64_t hub_count(const smore_ctx* c, int64_t V, int nb) {
     int64_t h = c->blk_hubs;
     if (const char* e = getenv("SMORE_HUBS")) h = atoll(e);
     if (h < 0) h = nb <= 4 ? 0 : std::min<int64_t>(HUB_AUTO, V / (8 * (int64_t)nb));
     return std::max<int64_t>(0, std::min(std::min(h, c->c_slots), V / 2));
+}
+
+// walk cells' write-combined W candidates: the part's rows [wlo, whi) that
+// are hot under the scaled source law
+std::vector<std::pair<double, int32_t>> hot_w_rows(const std::vector<double>& ps, int64_t wlo, int64_t whi, int nparts,
+                                                   int K, int64_t M, double tau) {
+    std::vector<std::pair<double, int32_t>> wcand;
+    // a W row's rate counts each record's 1 + K gradient terms against the
+    // pair budget (SMORE_WALK_WCOMB_X overrides the factor)
+    const char* xe = getenv("SMORE_WALK_WCOMB_X");
+    const double wx = xe ? atof(xe) : (double)(1 + K);
+    for (int64_t v = wlo; v < whi; ++v) {
+        const double p = ps[v] * nparts * wx;
+        if ((double)M * p > tau) wcand.push_back({p, (int32_t)(v | SH_WKEY)});
+    }
+    return wcand;
+}
+
+// the plan's host vectors, moved into the context
+void keep_plan(smore_ctx::Blocks& B, BlockPlan& P) {
+    B.wb = std::move(P.wb);
+    B.cb = std::move(P.cb);
+    B.mass = std::move(P.mass);
+    B.part_mass = std::move(P.part_mass);
+    B.nmass = std::move(P.nmass);
+    B.atom_off = std::move(P.atom_off);
+    B.hubs = std::move(P.hubs);
+    B.hub_rate = std::move(P.hub_rate);
+    B.hub_off = P.hub_off;
+    B.nhub = P.nhub;
+    B.hub_p = std::move(P.hub_p);
+    B.pmax_w = std::move(P.pmax_w);
+    B.pmax_c = std::move(P.pmax_c);
 }
 
 // the update-kernel arguments shared by a context's cell launches
@@ -445,7 +476,7 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
     const int64_t V = g.V;
     const int nb = 2 * nparts;
     if (V < nb) return fail(c, SMORE_EINVAL, "block schedule: fewer vertices than blocks");
-    const int64_t H = hub_count(c, V, nb, walk);
+    const int64_t H = hub_count(c, V, nb);
     char key[288];
     snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%lld/%lld/%d/%d/%d/%.9g/%lld/%s", model, nparts, part, K, mode,
              (long long)V, (long long)g.E, c->dpad, c->sh_max, c->sh_flush, c->hot_tau, (long long)H,
@@ -453,79 +484,10 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
     if (c->blk.key == key) return SMORE_OK;
     blocks_release(c);
     auto& B = c->blk;
-    B.n = nparts;
-    B.r = part;
-    B.nb = nb;
-    B.model = model;
-    B.K = K;
-    B.mode = mode;
-    std::vector<double> ps, pn, pc;
-    draw_probabilities(g, ps, pn, pc);
-    // hub C rows: the H rows with the most expected touches per sample (as
-    // a positive context plus K times as a negative); slot j is row V + j
-    std::vector<int32_t> hub_of;
-    double pnH = 0.0;
-    if (H > 0) {
-        std::vector<int32_t> idx((size_t)V);
-        std::iota(idx.begin(), idx.end(), 0);
-        auto q = [&](int32_t x) { return pc[x] + (double)K * pn[x]; };
-        std::partial_sort(idx.begin(), idx.begin() + H, idx.end(), [&](int32_t a, int32_t b) {
-            return q(a) > q(b) || (q(a) == q(b) && a < b);
-        });
-        hub_of.assign((size_t)V, -1);
-        B.hubs.assign(idx.begin(), idx.begin() + H);
-        B.hub_rate.resize((size_t)H);
-        for (int64_t j = 0; j < H; ++j) {
-            hub_of[B.hubs[j]] = (int32_t)j;
-            B.hub_rate[j] = q(B.hubs[j]);
-            pnH += pn[B.hubs[j]];
-        }
-        B.H = H;
-    }
-    source_bounds(ps, nparts, B.wb);
-    {   // C blocks of equal NON-hub negative mass (the hubs are in every block)
-        std::vector<double> pcut = pn;
-        for (int32_t x : B.hubs) pcut[x] = 0.0;
-        source_bounds(pcut, nb, B.cb);
-    }
-    for (int p = 0; p < nparts; ++p)
-        if (B.wb[p + 1] <= B.wb[p]) return fail(c, SMORE_EINVAL, "block schedule: an empty W part");
-    for (int k = 0; k < nb; ++k)
-        if (B.cb[k + 1] <= B.cb[k]) return fail(c, SMORE_EINVAL, "block schedule: an empty C block");
-    auto is_hub = [&](int64_t x) { return H > 0 && hub_of[x] >= 0; };
-    // NegativeSample's share of each block: its non-hub rows, plus 1/nb of
-    // every hub's (cell_args' negative weight)
-    std::vector<double> nraw((size_t)nb, 0.0);
-    {
-        B.nmass.assign((size_t)nb, 0.0);
-        double tot = 0.0;
-        for (int k = 0; k < nb; ++k) {
-            for (int64_t x = B.cb[k]; x < B.cb[k + 1]; ++x)
-                if (!is_hub(x)) nraw[k] += pn[x];
-            nraw[k] += pnH / nb;
-            tot += nraw[k];
-        }
-        for (int k = 0; k < nb; ++k) B.nmass[k] = tot > 0 ? nraw[k] / tot : 1.0 / nb;
-    }
-    // each part's share of the source law: a round's samples are split over
-    // the replicas by it (source_bounds only makes the parts roughly equal; a
-    // hub above 1/N of the mass puts a part far off)
-    {
-        B.part_mass.assign((size_t)nparts, 0.0);
-        double tot = 0.0;
-        for (int p = 0; p < nparts; ++p) {
-            for (int64_t v = B.wb[p]; v < B.wb[p + 1]; ++v) B.part_mass[p] += ps[v];
-            tot += B.part_mass[p];
-        }
-        for (double& m : B.part_mass) m = tot > 0 ? m / tot : 1.0 / nparts;
-    }
     // Hot tags (hybrid scatter) and the write-combined sets.  LINE-2: exact
-    // per cell from its atoms -- W row v: its atoms' share of the cell's mass;
-    // C row x: its atoms' share plus K times its share of the block's negative
-    // law -- so a row is atomic iff M * p > tau in the launch that trains it
-    // (a scaled global law misses the sources whose contexts crowd one block:
-    // up to nb times hotter in that cell).  Walks: the scaled global law
-    // (hot_maps.cpp build_hot_maps), whose tags the walk ids carry.
+    // per cell from its atoms (block_plan.cpp line2_cell_law).  Walks: the
+    // scaled global law (hot_maps.cpp build_hot_maps), whose tags the walk
+    // ids carry.
     const bool hyb = mode == SMORE_HYBRID;
     int64_t M = 0;
     double tau = 0.0;
@@ -544,280 +506,39 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
         tau = c->hot_tau >= 0 ? c->hot_tau : small ? 0.0 : tcell;
         if (walk && (rc = build_hot_maps(c, SMORE_LINE2, K, M, HOT_TAU_WALK, PAIR_FLUSH_MAX, (double)nparts, (double)nb))) return rc;
     }
-    const int T = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), (unsigned)nb);
-    auto par_blocks = [&](auto&& f) {
-        std::vector<std::thread> th;
-        for (int t = 0; t < T; ++t)
-            th.emplace_back([&, t] {
-                for (int k = t; k < nb; k += T) f(k);
-            });
-        for (auto& x : th) x.join();
-    };
-    // LINE-2 atoms of this part: the TargetSample outcomes of its sources,
-    // bucketed by the context's block -- bucket nb: the hub contexts (as
-    // slot ids), shared by every block's cell
-    const int NBK = nb + (H > 0 ? 1 : 0);
-    B.mass.assign((size_t)nb, 0.0);
-    B.hub_p.assign((size_t)nb, 0.0);
-    B.atom_off.assign((size_t)NBK + 1, 0);
-    std::vector<int32_t> av, ac;
-    std::vector<double> aw;
-    std::vector<double> hubw;   // LINE-2: per hub slot, the part's atom mass of that context
-    double mH = 0.0;
-    const int64_t wlo = B.wb[part], whi = B.wb[part + 1];
-    if (!walk) {
-        auto bucket_of = [&](int64_t x) {
-            if (is_hub(x)) return nb;
-            return (int)(std::upper_bound(B.cb.begin(), B.cb.end(), x) - B.cb.begin()) - 1;
-        };
-        auto id_of = [&](int64_t x) { return is_hub(x) ? (int32_t)(V + hub_of[x]) : (int32_t)x; };
-        // vertices [vb, ve) of the part, in order
-        auto each_atom = [&](int64_t vb, int64_t ve, auto&& f) {
-            for (int64_t v = vb; v < ve; ++v) {
-                const int64_t off = g.offsets[v], br = g.offsets[v + 1] - off;
-                if (br == 0 || ps[v] <= 0) continue;
-                const double s = ps[v] / (double)br;
-                for (int64_t i = 0; i < br; ++i) {
-                    const double pr = g.cprob[off + i];
-                    f(v, (int64_t)g.targets[off + i], s * pr);
-                    if (g.calias[off + i] >= 0 && pr < 1.0) f(v, g.calias[off + i], s * (1.0 - pr));
-                }
-            }
-        };
-        // two passes over vertex slices on every host thread (count per
-        // (slice, bucket), then fill); the slices' order keeps each bucket's
-        // atoms in vertex order, as one pass would
-        const int TS = (int)std::max(1u, std::min(std::thread::hardware_concurrency(), 64u));
-        std::vector<int64_t> vs((size_t)TS + 1);
-        {   // slices of equal edge count
-            const int64_t e0 = g.offsets[wlo], e1 = g.offsets[whi];
-            for (int t = 0; t <= TS; ++t) {
-                const int64_t e = e0 + (e1 - e0) * t / TS;
-                vs[t] = t == 0 ? wlo : t == TS ? whi
-                                 : std::lower_bound(g.offsets.begin() + wlo, g.offsets.begin() + whi, e) -
-                                       g.offsets.begin();
-            }
-        }
-        auto par_slices = [&](auto&& f) {
-            std::vector<std::thread> th;
-            for (int t = 0; t < TS; ++t) th.emplace_back([&, t] { f(t); });
-            for (auto& x : th) x.join();
-        };
-        std::vector<uint64_t> cnt((size_t)TS * NBK, 0);
-        par_slices([&](int t) {
-            uint64_t* ct = cnt.data() + (size_t)t * NBK;
-            each_atom(vs[t], vs[t + 1], [&](int64_t, int64_t x, double w) {
-                if (w > 0) ct[bucket_of(x)]++;
-            });
-        });
-        std::vector<uint64_t> start((size_t)TS * NBK);
-        for (int k = 0; k < NBK; ++k) {
-            uint64_t acc = B.atom_off[k];
-            for (int t = 0; t < TS; ++t) {
-                start[(size_t)t * NBK + k] = acc;
-                acc += cnt[(size_t)t * NBK + k];
-            }
-            B.atom_off[k + 1] = acc;
-        }
-        const uint64_t A = B.atom_off[NBK];
-        if (A == 0) return fail(c, SMORE_EINVAL, "block schedule: a part without edges");
-        av.resize(A);
-        ac.resize(A);
-        aw.resize(A);
-        par_slices([&](int t) {
-            uint64_t* pos = start.data() + (size_t)t * NBK;
-            each_atom(vs[t], vs[t + 1], [&](int64_t v, int64_t x, double w) {
-                if (w <= 0) return;
-                const uint64_t p = pos[bucket_of(x)]++;
-                av[p] = (int32_t)v;
-                ac[p] = id_of(x);
-                aw[p] = w;
-            });
-        });
-        std::vector<double> m((size_t)NBK, 0.0);
-        for (int k = 0; k < NBK; ++k)
-            for (uint64_t p = B.atom_off[k]; p < B.atom_off[k + 1]; ++p) m[k] += aw[p];
-        if (H > 0) {
-            mH = m[nb];
-            B.hub_off = B.atom_off[nb];
-            B.nhub = B.atom_off[nb + 1] - B.atom_off[nb];
-            hubw.assign((size_t)H, 0.0);
-            for (uint64_t p = B.hub_off; p < B.hub_off + B.nhub; ++p) hubw[ac[p] - V] += aw[p];
-        }
-        // a cell's mass: its block's atoms plus 1/nb of the part's hub atoms
-        double tot = 0.0;
-        for (int k = 0; k < nb; ++k) {
-            B.mass[k] = m[k] + mH / nb;
-            B.hub_p[k] = B.mass[k] > 0 ? (mH / nb) / B.mass[k] : 0.0;
-            tot += B.mass[k];
-        }
-        for (double& x : B.mass) x /= tot;
-    }
-    // per block: the C-row law of its cell (over [cb[k], cb[k+1]) then the H
-    // hub slots) and the flags of its C rows and (LINE-2) of this part's W rows
-    std::vector<std::vector<double>> pcb((size_t)nb);
-    std::vector<std::vector<uint8_t>> hcb((size_t)nb), hwb((size_t)nb);
-    // the hottest row of each cell (its launch's concurrency cap, cell_grid):
-    // walks the scaled global law, LINE-2 the cell's exact one
-    B.pmax_w.assign((size_t)nb, 0.0);
-    B.pmax_c.assign((size_t)nb, 0.0);
-    double wmax = 0.0;
-    for (int64_t v = wlo; v < whi; ++v) wmax = std::max(wmax, ps[v] * nparts);
-    {
-        par_blocks([&](int k) {
-            const int64_t lo = B.cb[k], n = B.cb[k + 1] - lo;
-            auto& pcx = pcb[k];
-            pcx.assign((size_t)(n + H), 0.0);
-            hcb[k].assign((size_t)(n + H), 0);
-            if (walk) {   // hot_maps.cpp build_hot_maps' scaled law (hot_pc); the hub slots at their global rate
-                double mx = 0.0;
-                for (int64_t i = 0; i < n; ++i) {
-                    pcx[i] = is_hub(lo + i) ? 0.0 : (pc[lo + i] + K * pn[lo + i]) * nb;
-                    hcb[k][i] = hyb && !is_hub(lo + i) ? c->hot_c[lo + i] : 0;
-                    mx = std::max(mx, pcx[i]);
-                }
-                for (int64_t j = 0; j < H; ++j) {
-                    pcx[n + j] = B.hub_rate[j];
-                    hcb[k][n + j] = hyb && (double)M * B.hub_rate[j] > tau;
-                    mx = std::max(mx, pcx[n + j]);
-                }
-                B.pmax_w[k] = wmax;
-                B.pmax_c[k] = mx;
-                return;
-            }
-            std::vector<double> pw((size_t)(whi - wlo), 0.0);
-            double mraw = 0.0;   // the cell's raw atom mass (its block's, plus 1/nb of the hub atoms')
-            for (uint64_t p = B.atom_off[k]; p < B.atom_off[k + 1]; ++p) {
-                pw[av[p] - wlo] += aw[p];
-                pcx[ac[p] - lo] += aw[p];
-                mraw += aw[p];
-            }
-            for (uint64_t p = B.hub_off; p < B.hub_off + B.nhub; ++p) pw[av[p] - wlo] += aw[p] / nb;
-            for (int64_t j = 0; j < H; ++j) pcx[n + j] = hubw[j] / nb;
-            mraw += mH / nb;
-            hwb[k].assign(pw.size(), 0);
-            double mw = 0.0, mc = 0.0;
-            for (size_t i = 0; i < pw.size(); ++i) {
-                hwb[k][i] = mraw > 0 && (double)M * pw[i] / mraw > tau;
-                if (mraw > 0) mw = std::max(mw, pw[i] / mraw);
-            }
-            const double pnb = nraw[k];
-            for (int64_t i = 0; i < n + H; ++i) {
-                const double pneg = i < n ? (is_hub(lo + i) ? 0.0 : pn[lo + i]) : pn[B.hubs[i - n]] / nb;
-                pcx[i] = (mraw > 0 ? pcx[i] / mraw : 0.0) + (pnb > 0 ? K * pneg / pnb : 0.0);
-                hcb[k][i] = (double)M * pcx[i] > tau;
-                mc = std::max(mc, pcx[i]);
-            }
-            B.pmax_w[k] = mw;
-            B.pmax_c[k] = mc;
-        });
-    }
-    // one tag per hub slot and per W row of the shared hub atoms (a row's
-    // tag must not depend on the cell that draws it): hot in any cell
-    std::vector<uint8_t> hubhot((size_t)H, 0), hwh;
-    if (H > 0 && hyb && walk) {
-        const int64_t n0 = B.cb[1] - B.cb[0];
-        for (int64_t j = 0; j < H; ++j) hubhot[j] = hcb[0][n0 + j];
-    } else if (H > 0 && hyb) {
-        hwh.assign((size_t)(whi - wlo), 0);
-        for (int k = 0; k < nb; ++k) {
-            const int64_t n = B.cb[k + 1] - B.cb[k];
-            for (int64_t j = 0; j < H; ++j) hubhot[j] |= hcb[k][n + j];
-            for (size_t i = 0; i < hwh.size(); ++i) hwh[i] |= hwb[k][i];
-        }
-        for (int k = 0; k < nb; ++k) {
-            const int64_t n = B.cb[k + 1] - B.cb[k];
-            for (int64_t j = 0; j < H; ++j) hcb[k][n + j] = hubhot[j];
-        }
-    }
-    auto hc = [&](int k, int64_t x) -> uint32_t {
-        if (!hyb) return 0u;
-        if (x >= V) return hubhot[x - V];
-        return hcb[k][x - B.cb[k]];
-    };
-    auto hw = [&](int k, int64_t v) -> uint32_t { return hyb && !walk ? hwb[k][v - wlo] : 0u; };
-    // negative tables: block k's law over its non-hub rows and 1/nb of every
-    // hub's (Go alias rule, power 1: any exact encoding of the law), ids
-    // absolute (hub slots V + j); entries of the rows in place, of the slots
-    // at [k * H, (k + 1) * H)
-    {
-        hvec<AliasEntry> nt((size_t)V);
-        std::vector<AliasEntry> hnt((size_t)nb * (size_t)H);
-        par_blocks([&](int k) {
-            const int64_t lo = B.cb[k], n = B.cb[k + 1] - lo, nn = n + H;
-            std::vector<double> wt((size_t)nn), prob((size_t)nn);
-            std::vector<int64_t> alias((size_t)nn);
-            std::vector<int32_t> self((size_t)nn);
-            auto id = [&](int64_t i) { return (int32_t)(i < n ? lo + i : V + (i - n)); };
-            for (int64_t i = 0; i < nn; ++i) {
-                wt[i] = i < n ? (is_hub(lo + i) ? 0.0 : pn[lo + i]) : pn[B.hubs[i - n]] / nb;
-                self[i] = id(i);
-            }
-            alias_go(wt.data(), nn, 1.0, prob.data(), alias.data());
-            for (int64_t i = 0; i < nn; ++i) alias[i] = id(alias[i]);
-            std::vector<AliasEntry> e((size_t)nn);
-            alias_encode(prob.data(), alias.data(), nn, self.data(), e.data());
-            for (int64_t i = 0; i < nn; ++i) {
-                const uint32_t al = (uint32_t)e[i].alias;
-                e[i].alias = (int32_t)(al | (hc(k, al) << 30) | (hc(k, self[i]) << 31));
-                if (i < n) nt[lo + i] = e[i];
-                else hnt[(size_t)k * H + (i - n)] = e[i];
-            }
-        });
-        if ((rc = upload(c, B.d_ntab, reinterpret_cast<const uint2*>(nt.data()), (size_t)V, true))) return rc;
-        if (H > 0) {
-            if ((rc = upload(c, B.d_hub_ntab, reinterpret_cast<const uint2*>(hnt.data()), hnt.size()))) return rc;
-            if ((rc = upload(c, B.d_hub_ids, B.hubs.data(), B.hubs.size()))) return rc;
-            if (walk) {   // the pair kernels' hub lookup: slot j | hot tag << 30
-                std::vector<int32_t> ho((size_t)V, -1);
-                for (int64_t j = 0; j < H; ++j) ho[B.hubs[j]] = (int32_t)(j | ((int64_t)hubhot[j] << 30));
-                if ((rc = upload(c, B.d_hub_of, ho.data(), ho.size()))) return rc;
-            }
-        }
-    }
-    // LINE-2: one alias table per block over its atoms and one over the part's
-    // hub atoms, tagged per cell (the hub atoms with their any-cell tags)
-    if (!walk) {
-        hvec<uint4> at((size_t)B.atom_off[NBK] * 2);
-        auto table = [&](int k, uint64_t a0, uint64_t n, bool hubs) {
-            if (n == 0) return;
-            std::vector<double> prob(n);
-            std::vector<int64_t> alias(n);
-            std::vector<AliasEntry> e(n);
-            alias_go(aw.data() + a0, (int64_t)n, 1.0, prob.data(), alias.data());
-            alias_encode(prob.data(), alias.data(), (int64_t)n, nullptr, e.data());
-            auto tw = [&](int32_t v) -> uint32_t { return hubs ? (hyb ? hwh[v - wlo] : 0u) : hw(k, v); };
-            for (uint64_t i = 0; i < n; ++i) {
-                const uint64_t s = a0 + i, a = a0 + (uint64_t)e[i].alias;
-                at[2 * s] = make_uint4(e[i].thresh, (uint32_t)av[s] | (tw(av[s]) << 30),
-                                       (uint32_t)ac[s] | (hc(k, ac[s]) << 30), 0u);
-                at[2 * s + 1] = make_uint4((uint32_t)av[a] | (tw(av[a]) << 30),
-                                           (uint32_t)ac[a] | (hc(k, ac[a]) << 30), 0u, 0u);
-            }
-        };
-        par_blocks([&](int k) { table(k, B.atom_off[k], B.atom_off[k + 1] - B.atom_off[k], false); });
-        if (H > 0) table(0, B.hub_off, B.nhub, true);
-        if ((rc = upload(c, B.d_atoms, at.data(), at.size(), true))) return rc;
-    }
+    DrawLaws laws;
+    draw_probabilities(g, laws.ps, laws.pn, laws.pc);
+    const BlockPlanArgs pa{walk, nparts, part, K, hyb, H, M, tau, walk && hyb ? c->hot_c.data() : nullptr};
+    BlockPlan P;
+    const std::string why = build_block_plan(g, laws, pa, P);
+    if (!why.empty()) return fail(c, SMORE_EINVAL, why);
+    B.n = nparts;
+    B.r = part;
+    B.nb = nb;
+    B.model = model;
+    B.K = K;
+    B.mode = mode;
+    B.H = H;
+    keep_plan(B, P);
     c->hot_M = M;
     std::vector<int2> hash;
     std::vector<int32_t> ids;
-    std::vector<std::pair<double, int32_t>> wcand;   // walk cells: the part's hot W rows (block_sh_sets)
-    if (walk && hyb && wcomb_on()) {
-        // a W row's rate counts each record's 1 + K gradient terms against the
-        // pair budget (SMORE_WALK_WCOMB_X overrides the factor)
-        const char* xe = getenv("SMORE_WALK_WCOMB_X");
-        const double wx = xe ? atof(xe) : (double)(1 + K);
-        for (int64_t v = wlo; v < whi; ++v) {
-            const double p = ps[v] * nparts * wx;
-            if ((double)M * p > tau) wcand.push_back({p, (int32_t)(v | SH_WKEY)});
-        }
-    }
-    block_sh_sets(c, walk, hyb && !small, M, pcb, hcb, hash, ids, wcand);
+    // walk cells: the part's hot W rows (block_sh_sets)
+    std::vector<std::pair<double, int32_t>> wcand;
+    if (walk && hyb && wcomb_on()) wcand = hot_w_rows(laws.ps, B.wb[part], B.wb[part + 1], nparts, K, M, tau);
+    block_sh_sets(c, walk, hyb && !small, M, P.pcb, P.hcb, hash, ids, wcand);
     if (getenv("SMORE_SH_DEBUG"))
         for (int k = 0; k < nb; ++k)
             fprintf(stderr, "[cell] part %d/%d block %d M %lld M*pmax_w %.4g M*pmax_c %.4g hubs %lld hub_p %.4g\n", part,
                     nparts, k, (long long)M, M * B.pmax_w[k], M * B.pmax_c[k], (long long)H, B.hub_p[k]);
+    if ((rc = upload(c, B.d_ntab, reinterpret_cast<const uint2*>(P.ntab.data()), (size_t)V, true))) return rc;
+    if (H > 0) {
+        if ((rc = upload(c, B.d_hub_ntab, reinterpret_cast<const uint2*>(P.hub_ntab.data()), P.hub_ntab.size()))) return rc;
+        if ((rc = upload(c, B.d_hub_ids, B.hubs.data(), B.hubs.size()))) return rc;
+        if (walk && (rc = upload(c, B.d_hub_of, P.hub_of.data(), P.hub_of.size()))) return rc;
+    }
+    if (!walk && (rc = upload(c, B.d_atoms, reinterpret_cast<const uint4*>(P.atoms.data()), P.atoms.size() / 4, true)))
+        return rc;
     if ((rc = upload(c, B.d_sh_hash, hash.data(), hash.size()))) return rc;
     if ((rc = upload(c, B.d_sh_ids, ids.data(), ids.size()))) return rc;
     B.key = key;

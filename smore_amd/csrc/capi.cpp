@@ -2,7 +2,8 @@
 // context, its graph and tables.  The source partition and the hot-row policy
 // are in hot_maps.cpp, the training drivers in train.cpp, the row transfers
 // and the multi-caller combiner in pairs_rows.cpp, the block schedule in
-// blocks.cpp, the replica exchange in exchange.cpp.
+// blocks.cpp and block_plan.cpp, the replica exchange in exchange.cpp, the
+// one-process group in group.cpp and group_blocks.cpp.
 //
 // A context owns one GPU's copy of the graph (CSR, encoded alias tables, the
 // fastSigmoid table) and the embedding tables.  Everything on the device is

@@ -1,8 +1,9 @@
 // ctx.h -- the library context (one GPU's graph, tables and buffers) and the
 // host-side helpers shared by the C ABI translation units (capi.cpp,
-// hot_maps.cpp, train.cpp, pairs_rows.cpp, blocks.cpp, exchange.cpp; what only
-// the training paths share is in train_host.h).  Internal: not part of the
-// installed interface.
+// hot_maps.cpp, train.cpp, pairs_rows.cpp, blocks.cpp, exchange.cpp, group.cpp,
+// group_blocks.cpp; what only the training paths share is in train_host.h,
+// what only the multi-GPU paths share in group.h).  Internal: not part of
+// the installed interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -119,7 +120,7 @@ struct smore_ctx {
     // the all-reduced deltas R per table, a communicator and its stream
     void* comm = nullptr;               // ncclComm_t (a same-device group: the group, no RCCL)
     bool own_comm = false;              // created by smore_comm_init (destroyed with the context)
-    bool local_comm = false;            // replica of a same-device group (exchange.cpp local collectives)
+    bool local_comm = false;            // replica of a same-device group (group.cpp local collectives)
     int nranks = 1, rank = 0;
     hipStream_t comm_stream = nullptr;
     hipEvent_t ex_ready = nullptr, ex_done = nullptr;
@@ -158,7 +159,7 @@ struct smore_ctx {
     std::vector<double> census_rate[2];
     bool census_ok = false;
     uint64_t census_gen = 0;            // bumped by every smore_census_end (the adaptive scales' key)
-    std::string census_key;             // what the group driver censused (exchange.cpp)
+    std::string census_key;             // what the group driver censused (group.cpp)
     // caller-supplied pairs (smore_train_pairs): a chunk of (v, c) on the device
     int32_t* d_pairs = nullptr;
     size_t pairs_cap = 0;               // int32 words (two per pair)

@@ -123,6 +123,10 @@ class GlibcRand {
 void draw_probabilities(const HostGraph& g, std::vector<double>& p_src, std::vector<double>& p_neg,
                         std::vector<double>& p_ctx, const std::vector<double>* src_law = nullptr);
 
+// Part bounds of a law over the vertices (the midpoint rule): n contiguous id
+// ranges of (nearly) equal mass, bound[p] .. bound[p + 1] - 1 is part p.
+void source_bounds(const std::vector<double>& ps, int n, std::vector<int64_t>& bound);
+
 // DeepWalk walk-start order (src/model/DeepWalk.cpp:122-131).
 void deepwalk_order(int64_t V, int walk_times, uint64_t skip, int64_t* order);
 

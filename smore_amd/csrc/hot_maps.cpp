@@ -15,25 +15,6 @@ using namespace smore_host;
 namespace smore_host {
 
 // ---------------------------------------------------------------- source partition
-// Part bounds of the current (global) source law: vertex v belongs to the part
-// holding the midpoint of its probability mass, so parts are contiguous id
-// ranges of (nearly) equal mass; bound[p] .. bound[p + 1] - 1 is part p.
-void source_bounds(const std::vector<double>& ps, int n, std::vector<int64_t>& bound) {
-    const int64_t V = (int64_t)ps.size();
-    double total = 0.0;
-    for (double p : ps) total += p;
-    bound.assign((size_t)n + 1, V);
-    bound[0] = 0;
-    double cum = 0.0;
-    int next = 1;
-    for (int64_t v = 0; v < V && next < n; ++v) {
-        const double mid = (cum + 0.5 * ps[v]) / total;
-        const int owner = std::min(n - 1, (int)std::floor(mid * n));
-        while (next <= owner && next < n) bound[next++] = v;
-        cum += ps[v];
-    }
-}
-
 // the source law restricted to part i of n and renormalised
 static void partition_law(const std::vector<double>& ps, int n, int i, std::vector<double>& law) {
     std::vector<int64_t> bound;

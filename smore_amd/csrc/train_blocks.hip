@@ -24,7 +24,7 @@
 // its block's restricted law (same slots as pair_emit_kernel, the index drawn
 // over the block).  Buckets keep walk order, so a bucket's records are the
 // one-GPU records restricted to the cell, in order.  The group driver walks
-// 1/N of a round per GPU and broadcasts the slices (exchange.cpp); the count
+// 1/N of a round per GPU and broadcasts the slices (group_blocks.cpp); the count
 // and the emit run one wave per walk (block_pairs_wave_kernel).
 #include "train_kernels.h"
 

@@ -31,7 +31,6 @@ int ensure_cap(smore_ctx* c, T*& p, size_t& cap, size_t need) {
 }
 
 // ---------------------------------------------------------------- hot_maps.cpp
-void source_bounds(const std::vector<double>& ps, int n, std::vector<int64_t>& bound);
 int apply_partition(smore_ctx* c);
 
 // the 2-D block schedule's per-cell concurrency cap (blocks.cpp cell_grid):

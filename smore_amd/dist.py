@@ -226,7 +226,7 @@ def adaptive_scale(rate, updates, world, c0=64.0):
 
 class BlockSync:
     """The 2-D block schedule over torch.distributed (one process per GPU;
-    the group driver's twin is exchange.cpp group_block_*).
+    the group driver's twin is group_blocks.cpp group_block_*).
 
     Rank r owns the W rows of part r; the C rows are cut into nb = 2N blocks
     (`c_bounds`, nb + 1 row bounds).  Sub-round s (counted over the whole run)

@@ -1,10 +1,10 @@
 """The 2-D block schedule's draw tables restated in numpy over the oracle's
-graph (test infrastructure: the checker of smore_amd/csrc/blocks.cpp and
-train_blocks.hip, never the product).
+graph (test infrastructure: the checker of smore_amd/csrc/block_plan.cpp,
+blocks.cpp and train_blocks.hip, never the product).
 
 A context that is part r of N (smore_block_setup) holds:
   * W part bounds: contiguous ids of equal source mass (the midpoint rule of
-    hot_maps.cpp source_bounds) under the source law SourceSample draws
+    host_graph.cpp source_bounds) under the source law SourceSample draws
     (src/proNet.cpp:647-657);
   * 2N C block bounds: the same rule over NegativeSample's law (:623-633);
   * per C block k, the negative law restricted to the block, as a Go-rule
@@ -70,7 +70,7 @@ def hub_count(V, nb, hubs=-1, c_slots=None):
 
 
 class BlockSpec:
-    """One part's block tables (blocks.cpp smore_block_setup, LINE-2), with the
+    """One part's block tables (block_plan.cpp build_block_plan, LINE-2), with the
     hub C rows: the H rows of the largest pc + K pn (ties to the lower id) are
     slots V + j, drawn in every block -- contexts through the part's hub atoms
     (a cell takes one iff Philox word 2 < its hub threshold), negatives through

@@ -5,7 +5,7 @@ after finish() every rank holds exactly the tables of ONE shared table pair
 trained cell by cell in the same order -- the schedule is the reference's
 single table (src/model/LINE.cpp:160-191) with the samples grouped by cell.
 Also the group driver's sample split: rounds, replica slices and the
-largest-remainder cell counts (exchange.cpp group_block_edges)."""
+largest-remainder cell counts (group_blocks.cpp group_block_edges)."""
 import os
 import socket
 
@@ -96,7 +96,7 @@ def test_block_rotation_gloo(world, subrounds):
 
 
 def test_group_block_split():
-    """exchange.cpp group_block_edges' split restated (bench.py reuses it):
+    """group_blocks.cpp group_block_edges' split restated (bench.py reuses it):
     the rounds tile [0, count), every replica's slice is split over its cells
     exactly, in sub-round order, with consecutive sample ranges."""
     from bench import block_schedule, largest_remainder
@@ -129,7 +129,8 @@ def test_part_mass_split_on_a_skewed_graph(tmp_path):
     split (largest remainder over the part masses) gives it that
     share of every round's samples, and the union of the parts' laws is the
     global source law (needs no GPU: the host side of smore_block_setup is
-    restated by tests/block_spec.py)."""
+    restated by tests/block_spec.py; test_block_plan_cpu.py holds the product's
+    plan, block_plan.cpp, to the same masses on the same graph)."""
     import numpy as np
     from tests.block_spec import part_masses
     from bench import largest_remainder

@@ -1,5 +1,5 @@
 """The 2-D block schedule of the multi-GPU path (blocks.cpp, train_blocks.hip,
-exchange.cpp group_block_*) on one MI355X:
+group_blocks.cpp group_block_*) on one MI355X:
   * a cell's draws are bit-exact against the numpy restatement of its tables
     (tests/block_spec.py: bounds, per-block negative tables, atoms), every
     source in the part, every context and negative in the block;
@@ -165,7 +165,7 @@ def _hub_exchange(n, V, Cs, Ss, Ds, Rs, sc, pending):
 
 
 def _schedule_edges(smore, graph, n, begin, count, per, total, K, dim, W0, C0, hubs=-1):
-    """exchange.cpp group_block_edges restated: rounds of per * n samples
+    """group_blocks.cpp group_block_edges restated: rounds of per * n samples
     split over the replicas by their parts' source mass (largest remainder),
     replica r's slice split over the blocks by its mass, sub-round s trains
     cell (r, (2r + s) mod 2n) on replica r's tables and its own copy of the

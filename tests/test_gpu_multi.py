@@ -1,6 +1,6 @@
 """Multi-GPU replica exchange on one MI355X:
   * the library's own RCCL path (smore_comm_init / smore_exchange_*,
-    exchange.cpp) at world size 1, where every exchange must add exactly zero;
+    exchange.cpp, group.cpp) at world size 1, where every exchange must add exactly zero;
   * a 1-replica smore_group_* run equals the single-context run;
   * two processes sharing the GPU, exchanging deltas through the fused HIP
     passes (replica_sync.hip) around a gloo all-reduce: the replicas agree
@@ -89,7 +89,7 @@ def test_group_of_one_equals_single_context(smore):
 
 
 def test_group_of_one_walk_models_equal_single_context(smore):
-    """smore_group_train_walklets / _app / _hpe (exchange.cpp) on one replica
+    """smore_group_train_walklets / _app / _hpe (group.cpp) on one replica
     are the single-context calls."""
     ref = _fresh(smore)
     g = smore.Group([0])
@@ -204,7 +204,7 @@ def test_n_ranks_replicas_agree_and_train_like_one(tmp_path, world):
 
 
 def test_group_of_one_go_walk_models_equal_single_context(smore):
-    """smore_group_train_node2vec / _metapath2vec / _ctdne (exchange.cpp) and the
+    """smore_group_train_node2vec / _metapath2vec / _ctdne (group.cpp) and the
     group setters on one replica are the single-context calls."""
     from smore_amd.go_models import load_hetero, load_temporal
     golden = os.path.join(ROOT, "tests", "golden")
@@ -359,7 +359,7 @@ def test_local_group_rounds_split_the_range(smore):
 
 
 def _emulate_group_walks(g, n, per, rule, W0, C0, dim, wt, steps, window, K, alpha0, order):
-    """The group driver's rounds and one-late exchange (exchange.cpp
+    """The group driver's rounds and one-late exchange (group.cpp
     group_rounds, replica_sync.hip delta_begin / delta_cycle / delta_end,
     local_sum) restated in fp32 numpy around the oracle's serial DeepWalk."""
     count = wt * g.V

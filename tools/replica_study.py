@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Multi-GPU replica quality through the library's own group driver
-(smore_group_*, exchange.cpp), with N replicas on ONE GPU (the group's local
+(smore_group_*, group.cpp), with N replicas on ONE GPU (the group's local
 collectives): the same rounds, source partition, adaptive scales (row census
 for the walk models) and one-late exchange as an N-GPU group, only the
 all-reduce is a device pass.  DESIGN.md 10.

@@ -507,6 +507,32 @@ int smore_train_app_async(smore_ctx* ctx, uint64_t unit_begin, uint64_t unit_end
 int smore_train_hpe_async(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, int walk_steps,
                           int K, double reg, double alpha0, uint64_t seed, int mode);
 
+/* replaces: WARP::Train (src/model/WARP.cpp:55-108) over samples [begin,
+ * begin + count) of `total`: v = SourceSample, i = TargetSample(v), then
+ * UpdateWARPPair (src/proNet.cpp:1353-1403) on the ONE table (the reference
+ * passes w_vertex twice): negatives j are drawn one at a time, at most 32,
+ * until f = T[v].(T[i] - T[j]) < 1; that trial updates the three rows (decay
+ * alpha * 0.0025 each, T[i] += g T[v], T[j] -= g T[v], T[v] += g (T[i] - T[j]),
+ * g = fastSigmoid(-f) * alpha) and ends the sample; 32 trials with f >= 1
+ * change nothing.  Draws: stream 0, unit = sample index, slots 0-3 source and
+ * target, slots 4 + 2n, 5 + 2n the negative of trial n -- a prefix whose
+ * length depends on the tables.  alpha: count from 0 (the BPR law).  Needs
+ * the negative method the caller wants (the reference sets "no_degrees").
+ * mode: SMORE_SERIAL | SMORE_HOGWILD | SMORE_ATOMIC; SMORE_HYBRID runs the
+ * atomic scatter (smore_last_mode reports SMORE_ATOMIC).  SMORE_HOGWILD
+ * (plain stores) runs at most (effective rows of the graph's source and
+ * positive-item laws) / 32 sample groups at a time, because colliding stores
+ * lose updates; the atomic scatter has no such cap.  One GPU; C++
+ * semantics only; not while a row census is open. */
+int smore_train_warp(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, double alpha0,
+                     uint64_t seed, int mode);
+int smore_train_warp_async(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, double alpha0,
+                           uint64_t seed, int mode);
+/* trials executed (f evaluations) and samples that updated, summed over every
+ * smore_train_warp call since smore_alloc_tables (which zeroes them); waits
+ * for the context stream */
+int smore_warp_stats(smore_ctx* ctx, uint64_t* trials, uint64_t* updated);
+
 /* replaces: proNet::UpdatePairs (src/proNet.cpp:2741-2753) and Go
  * (*ProNet).UpdatePairs (pkg/pronet/optimizer.go:8-18): UpdatePair for each
  * caller-supplied pair (v[i], c[i]), i = 0 .. n-1 in order, with K <= 10

@@ -135,6 +135,9 @@ def _load():
         "smore_train_walklets_async": (i32, [P, u64, u64, i32, i32, i32, i32, i32, dbl, u64, i32]),
         "smore_train_app_async": (i32, [P, u64, u64, i32, i32, dbl, i32, dbl, u64, P, i32]),
         "smore_train_hpe_async": (i32, [P, u64, u64, u64, i32, i32, dbl, dbl, u64, i32]),
+        "smore_train_warp": (i32, [P, u64, u64, u64, dbl, u64, i32]),
+        "smore_train_warp_async": (i32, [P, u64, u64, u64, dbl, u64, i32]),
+        "smore_warp_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),
         "smore_group_train_walklets": (i32, [P, u64, u64, i32, i32, i32, i32, i32, dbl, u64, i32, u64, i32]),
         "smore_group_train_app": (i32, [P, u64, u64, i32, i32, dbl, i32, dbl, u64, P, i32, u64, i32]),
         "smore_group_train_hpe": (i32, [P, u64, u64, u64, i32, i32, dbl, dbl, u64, i32, u64, i32]),

@@ -1,0 +1,61 @@
+// warp -- flag-compatible replacement of cli/warp.cpp (WARP, UpdateWARPPair:
+// up to 32 lazily drawn negatives per sample, one update on the first that
+// violates the margin; src/proNet.cpp:1353-1403).  Extra flags: -device,
+// -mode hogwild|atomic|hybrid|serial, -seed, -format cpp|go.  One GPU only.
+#include "cli_common.h"
+
+int main(int argc, char** argv) {
+    int i;
+    if (argc == 1) {
+        printf("[smore-mi355x] WARP\n\nOptions Description:\n");
+        printf("\t-train <string>\n\t-save <string>\n\t-dimensions <int> (64)\n\t-sample_times <int> (10, x10^6)\n");
+        printf("\t-alpha <float> (0.025)\n\t-threads <int>\n");
+        printf("\t-device <int> -mode hogwild|atomic|hybrid|serial -seed <int> -format cpp|go\n");
+        printf("Usage:\n./warp -train net.txt -save rep.txt -dimensions 64 -sample_times 10 -alpha 0.025 -threads 1\n");
+        return 0;
+    }
+    char network_file[4096] = "", rep_file[4096] = "";
+    int dimensions = 64, sample_times = 10, threads = 1, device = 0, gpus = 1, fmt = 0;
+    int mode = SMORE_HYBRID;
+    unsigned long long seed = 1;
+    double init_alpha = 0.025, reg = 0.01;
+    if ((i = ArgPos("-train", argc, argv)) > 0) snprintf(network_file, sizeof network_file, "%s", argv[i + 1]);
+    if ((i = ArgPos("-save", argc, argv)) > 0) snprintf(rep_file, sizeof rep_file, "%s", argv[i + 1]);
+    if ((i = ArgPos("-dimensions", argc, argv)) > 0) dimensions = atoi(argv[i + 1]);
+    if ((i = ArgPos("-sample_times", argc, argv)) > 0) sample_times = atoi(argv[i + 1]);
+    if ((i = ArgPos("-alpha", argc, argv)) > 0) init_alpha = atof(argv[i + 1]);
+    if ((i = ArgPos("-threads", argc, argv)) > 0) threads = atoi(argv[i + 1]);
+    if ((i = ArgPos("-device", argc, argv)) > 0) device = atoi(argv[i + 1]);
+    if ((i = ArgPos("-gpus", argc, argv)) > 0) gpus = atoi(argv[i + 1]);
+    if ((i = ArgPos("-mode", argc, argv)) > 0) mode = mode_of(argv[i + 1]);
+    if ((i = ArgPos("-seed", argc, argv)) > 0) seed = strtoull(argv[i + 1], 0, 10);
+    if ((i = ArgPos("-format", argc, argv)) > 0) fmt = !strcmp(argv[i + 1], "go");
+    if (gpus > 1) {
+        fprintf(stderr, "warp: -gpus %d: WARP runs on one GPU (no multi-GPU schedule for it)\n", gpus);
+        return 1;
+    }
+
+    Run run = open_run(device, 1);
+    smore_ctx* ctx = run.ctx;
+    // WARP() sets negative_method "no_degrees" (src/model/WARP.cpp:4-7); LoadEdgeList(file, 0)
+    run_load(run, network_file, 0, SMORE_VM_OUT_DEGREES, SMORE_NM_NO_DEGREES);
+    print_graph(ctx);
+    printf("Model Setting:\n\tdimension:\t\t%d\n", dimensions);
+    run_alloc(run, dimensions, 1);
+    SMORE_CLI_CHECK(ctx, smore_init_table_glibc(ctx, SMORE_W, 0));
+    run_replicate(run);
+    printf("Model:\n\t[WARP]\nLearning Parameters:\n\tsample_times:\t\t%d\n\talpha:\t\t\t%g\n"
+           "\tregularization:\t\t%g\n\tworkers:\t\t%d\nStart Training:\n", sample_times, init_alpha, reg, threads);
+    const unsigned long long total = (unsigned long long)sample_times * 1000000ull, chunk = 1ull << 26;
+    for (unsigned long long done = 0; done < total;) {
+        const unsigned long long n = total - done < chunk ? total - done : chunk;
+        SMORE_CLI_CHECK(ctx, smore_train_warp(ctx, done, n, total, init_alpha, seed, mode));
+        done += n;
+        printf("\tProgress: %.3f %%%c", (double)done / total * 100, 13);
+        fflush(stdout);
+    }
+    printf("\tProgress: 100.00 %%\n");
+    save(ctx, rep_file, fmt);
+    run_close(run);
+    return 0;
+}

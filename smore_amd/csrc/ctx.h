@@ -40,6 +40,8 @@ struct smore_ctx {
     float* d_sig = nullptr;
     unsigned long long* d_skipped = nullptr;
     unsigned long long* d_work = nullptr;   // chunk counter of the Hogwild edge kernels
+    unsigned long long* d_warp_stats = nullptr;   // WARP: {trials executed, samples that updated} (smore_warp_stats)
+    double warp_rows = 0.0;             // WARP: effective rows of the plain-store cap (train_warp.cpp; 0: not computed)
     // tables
     float* d_table[2] = {nullptr, nullptr};
     int dim = 0, dpad = 0, ntables = 0;
@@ -327,6 +329,7 @@ inline int upload_graph(smore_ctx* c) {
     c->census_key.clear();
     c->census_rate[0].clear();
     c->census_rate[1].clear();
+    c->warp_rows = 0.0;
     dfree(c->d_census[0]);
     dfree(c->d_census[1]);
     blocks_release(c);

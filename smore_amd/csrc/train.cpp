@@ -26,7 +26,7 @@ static hipError_t launch_go_rec(const EdgeArgs& a, int grid, hipStream_t st) {
 }
 
 // kind: 0 the C++ edge/pair kernel, 1 Go records (go_rec_kernel), 2 Go walk
-// pairs (go_pair_kernel)
+// pairs (go_pair_kernel), 3 WARP (warp_train_kernel)
 int edge_grid(smore_ctx* c, const EdgeArgs& a, bool leave_slot, int kind) {
     if (a.mode == SMORE_SERIAL) return 1;
     int per_cu = 0;
@@ -34,6 +34,7 @@ int edge_grid(smore_ctx* c, const EdgeArgs& a, bool leave_slot, int kind) {
                       : kind == 2 ? (a.mode == SMORE_ATOMIC   ? go_pair_symbol_a(a)
                                      : a.mode == SMORE_HYBRID ? go_pair_symbol_h(a)
                                                               : go_pair_symbol_s(a))
+                      : kind == 3 ? (a.mode == SMORE_ATOMIC ? warp_symbol_a(a.dpad) : warp_symbol_s(a.dpad))
                                   : edge_kernel_symbol(a);
     if (!sym ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sym, 256, sh_lds_bytes(a.sh_rows, a.dpad)) !=

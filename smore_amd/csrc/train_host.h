@@ -80,7 +80,7 @@ int ensure_packed(smore_ctx* c);
 
 // ---------------------------------------------------------------- train.cpp
 // the update launch's grid.  kind: 0 the C++ edge/pair kernel, 1 Go records
-// (go_rec_kernel), 2 Go walk pairs (go_pair_kernel)
+// (go_rec_kernel), 2 Go walk pairs (go_pair_kernel), 3 WARP (warp_train_kernel)
 int edge_grid(smore_ctx* c, const EdgeArgs& a, bool leave_slot = false, int kind = 0);
 int grow_events(smore_ctx* c, std::vector<hipEvent_t>& v, size_t n);
 // the update-kernel arguments every record path fills alike (the tables by

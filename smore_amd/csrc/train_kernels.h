@@ -224,6 +224,31 @@ SMORE_DECL_PAIR(h5) SMORE_DECL_PAIR(h10)
 // (alpha_rec) in the Hogwild modes to pair_train_kernel
 hipError_t launch_edge_train(const EdgeArgs& a, int grid, hipStream_t st);
 const void* edge_kernel_symbol(const EdgeArgs& a);
+// WARP (warp_kernels.h; train_warp_<s|a>.hip): the update kernel draws the
+// negatives of trials 1..31 itself
+constexpr int WARP_TRIALS = 32;              // src/proNet.cpp:1366
+constexpr int WARP_KMAX = 5;                 // record width of the K = 1 draw
+enum { WARP_STORE = 0, WARP_ATOMIC = 1 };
+
+struct WarpArgs {
+    DevGraph g;
+    const float* sig;              // 1001-entry fastSigmoid table
+    float* T;                      // [V][dpad], the one table
+    const int32_t* rec;            // {v, i, j0, -1 ..} per sample, rec_width(WARP_KMAX) words (tagged ids)
+    unsigned long long* work;      // chunk counter, zeroed per launch
+    unsigned long long* stats;     // {trials executed, samples that updated}, accumulated
+    uint64_t begin, count, total, seed;
+    double alpha0;
+    int dpad, mode;                // mode: SMORE_* scatter (2 = serial)
+    int groups;                    // sample groups of a block that take samples (<= 256 / G; the rest idle)
+};
+
+// launch and occupancy symbol per scatter (train_warp_<s|a>.hip)
+hipError_t launch_warp_s(const WarpArgs& a, int grid, hipStream_t st);
+hipError_t launch_warp_a(const WarpArgs& a, int grid, hipStream_t st);
+const void* warp_symbol_s(int dpad);
+const void* warp_symbol_a(int dpad);
+
 hipError_t launch_sample(const DevGraph& g, uint64_t seed, uint64_t begin, uint64_t count, int K,
                          int bpr, int32_t* out, hipStream_t st);
 // 2-D block schedule (train_blocks.hip, blocks.cpp): C blocks <= BLOCK_MAX (N <= 16 W parts)

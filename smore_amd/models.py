@@ -1,5 +1,5 @@
 """Model drivers mirroring the reference's C++ model classes
-(src/model/{LINE,MF,BPR,DeepWalk,Walklets,APP,HPE}.h): LoadEdgeList / Init / Train / SaveWeights
+(src/model/{LINE,MF,BPR,WARP,DeepWalk,Walklets,APP,HPE}.h): LoadEdgeList / Init / Train / SaveWeights
 with the same argument meaning, banners and learning-rate schedule.  The hot
 loop is one HIP launch per chunk through the C ABI.
 
@@ -138,6 +138,38 @@ class BPR(_EdgeModel):
         print("Start Training:")
         total = int(sample_times) * 1000000
         self._run(total, total, 5, alpha, 0.0)
+
+
+class WARP(_EdgeModel):
+    """WARP (src/model/WARP.{h,cpp}): UpdateWARPPair on one table -- negatives
+    drawn one at a time (at most 32) until one violates the margin, then one
+    update of the three rows.  "hybrid" runs the atomic scatter."""
+
+    def __init__(self, device=0, mode="hybrid", seed=1):
+        super().__init__(device, mode, seed)
+        self.pnet.SetNegativeMethod("no_degrees")   # src/model/WARP.cpp:4-7
+
+    def Init(self, dim):
+        print("Model Setting:\n\tdimension:\t\t%d" % dim)
+        self.dim = dim
+        self.pnet.alloc_tables(dim, 1)
+        self.pnet.init_table_glibc(_lib.W, 0)       # src/model/WARP.cpp:45-50
+
+    def Train(self, sample_times, negative_samples, alpha, reg, workers=1):
+        # `negative_samples` and `reg` are ignored by the reference rule
+        # (src/proNet.cpp:1353-1403: up to 32 trials, decay 0.0025); reg is printed
+        print("Model:\n\t[WARP]\nLearning Parameters:")
+        print("\tsample_times:\t\t%d\n\talpha:\t\t\t%g\n\tregularization:\t\t%g\n\tworkers:\t\t%d"
+              % (sample_times, alpha, reg, workers))
+        print("Start Training:")
+        total = int(sample_times) * 1000000
+        done = 0
+        while done < total:
+            n = min(CHUNK, total - done)
+            self.pnet.train_warp(done, n, total, alpha, self.seed, self.mode)
+            done += n
+            _progress(_alpha_at(done, alpha, total), done / total)
+        _progress(_alpha_at(total, alpha, total), 1.0, "\n")
 
 
 class DeepWalk(_EdgeModel):

@@ -479,6 +479,18 @@ class ProNet:
         self._chk(lib.smore_train_hpe(self.ctx, int(begin), int(count), int(total), int(walk_steps), int(K),
                                       float(reg), float(alpha0), int(seed), _lib.MODE[mode]), "train_hpe")
 
+    def train_warp(self, begin, count, total, alpha0, seed=1, mode="hogwild", sync=True):
+        """WARP::Train (src/model/WARP.cpp:55-108) over samples [begin, begin + count) of total."""
+        fn = lib.smore_train_warp if sync else lib.smore_train_warp_async
+        self._chk(fn(self.ctx, int(begin), int(count), int(total), float(alpha0), int(seed), _lib.MODE[mode]),
+                  "train_warp")
+
+    def warp_stats(self):
+        """(trials executed, samples that updated) of the WARP calls since alloc_tables."""
+        t, u = C.c_uint64(), C.c_uint64()
+        self._chk(lib.smore_warp_stats(self.ctx, C.byref(t), C.byref(u)), "warp_stats")
+        return t.value, u.value
+
     def set_semantics(self, semantics):
         """"cpp" (src/proNet.cpp rules, default) or "go" (pkg/pronet rules)."""
         self._chk(lib.smore_set_semantics(self.ctx, _lib.SEM[semantics]), "set_semantics")

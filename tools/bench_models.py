@@ -15,6 +15,8 @@ calls after one warmup call, inputs resident in HBM.
 
     python tools/bench_models.py --configs c2 c3 c5 [--mode hybrid]
   c5go / c5n2v  Go DeepWalk / Go node2vec (p 0.5, q 2) on c5's graph
+  warp WARP on c3's graph, d=128 (M WARP samples/s, and the mean trials per
+       sample from smore_warp_stats; "hybrid" runs the atomic scatter)
 """
 import argparse
 import json
@@ -67,11 +69,11 @@ def main():
     import smore_amd
     from smore_amd import graphgen
     for cfg in args.configs:
-        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else cfg)
+        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg == "warp" else cfg)
         pn = smore_amd.ProNet(0)
         t0 = time.perf_counter()
-        if cfg == "c3":
-            pn.SetNegativeMethod("no_degrees")       # BPR() (src/model/BPR.cpp:4-7)
+        if cfg in ("c3", "warp"):
+            pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
         pn.set_graph_edges(V, src, dst, w)
         build = time.perf_counter() - t0
         out = {"config": cfg, "vertices": V, "edge_slots": pn.MAX_line, "mode": args.mode,
@@ -92,6 +94,24 @@ def main():
             out.update(model="bpr", dim=128, rounds=5, samples_per_call=S, ms_per_call=round(ms, 3),
                        draw_update_ms=ph,
                        value=round(S / ms / 1e3, 1), unit="M BPR samples/s (5 rounds each)")
+        elif cfg == "warp":
+            S = 1 << 26
+            pn.alloc_tables(128, 1)
+            pn.init_table_uniform(0, 1)
+            total = (args.steps + 1) * S
+            ms, ph, st = [], [], []
+            for k in range(args.steps + 1):
+                pn.train_warp(k * S, S, total, 0.025, 7, args.mode)
+                st.append(pn.warp_stats())
+                if k:
+                    ms.append(pn.last_kernel_ms())
+                    ph.append(pn.last_phase_ms()[:2])
+            ms = float(np.mean(ms))
+            out.update(model="warp", dim=128, samples_per_call=S, ms_per_call=round(ms, 3),
+                       draw_update_ms=[round(float(x), 3) for x in np.mean(ph, axis=0)],
+                       trials_per_sample=round((st[-1][0] - st[0][0]) / (args.steps * S), 4),
+                       updated_per_sample=round((st[-1][1] - st[0][1]) / (args.steps * S), 4),
+                       value=round(S / ms / 1e3, 1), unit="M WARP samples/s")
         elif cfg == "c5":
             steps_, window, K, walk_times = 40, 5, 5, 1
             pn.alloc_tables(128, 2)

@@ -14,7 +14,7 @@ OBJ      ?= build/obj
 LIB      ?= smore_amd/lib/libsmore_hip.so
 BIN      := smore_amd/bin
 # kernels depend on the device headers only; host objects on the host headers
-DEV_HDRS := $(SRC)/device_common.h $(SRC)/train_kernels.h $(SRC)/edge_kernels.h $(SRC)/edge_inst.h
+DEV_HDRS := $(SRC)/device_common.h $(SRC)/train_kernels.h $(SRC)/edge_kernels.h $(SRC)/edge_inst.h include/smore_hip.h
 HOST_HDRS := $(SRC)/host_graph.h $(SRC)/ctx.h $(SRC)/train_host.h $(SRC)/train_kernels.h $(SRC)/device_common.h $(SRC)/go_walks.h \
              $(SRC)/hot_exchange.h $(SRC)/comm_watch.h $(SRC)/group.h $(SRC)/block_plan.h include/smore_hip.h
 
@@ -35,7 +35,7 @@ $(OBJ)/%.o: $(SRC)/%.hip $(DEV_HDRS)
 # the Go walk kernels also depend on the CTDNE declarations; the Go record
 # kernels on go_rec.h; the exchange passes on their declarations
 $(OBJ)/train_go.o: $(SRC)/go_walks.h
-$(OBJ)/train_go_rec_s.o $(OBJ)/train_go_rec_a.o $(OBJ)/train_go_rec_h.o: $(SRC)/go_rec.h $(SRC)/go_walks.h
+$(OBJ)/train_go_rec_s.o $(OBJ)/train_go_rec_a.o $(OBJ)/train_go_rec_h.o: $(SRC)/go_rec.h
 $(OBJ)/replica_sync.o: $(SRC)/hot_exchange.h
 $(OBJ)/train_warp_s.o $(OBJ)/train_warp_a.o: $(SRC)/warp_kernels.h
 

@@ -67,7 +67,7 @@ int64_t resident_groups(smore_ctx* c, bool walk, int K, int mode) {
     a.count = (uint64_t)1 << 30;
     a.alpha_rec = walk ? 1 : 0;
     a.sh_rows = mode == SMORE_HYBRID ? std::min(c->sh_max, sh_rows_max(c->dpad)) : 0;
-    return (int64_t)edge_grid(c, a) * (256 / lanes_of(c->dpad));
+    return (int64_t)edge_grid(c, UpdateFamily::Cpp, a) * (256 / lanes_of(c->dpad));
 }
 
 // per-block write-combined rows: the hottest hot C rows of each block under
@@ -258,7 +258,7 @@ EdgeArgs cell_args(smore_ctx* c, int k, bool walk) {
 // flight (C5 DeepWalk, 8 GPUs) diverges whether the row is atomic or
 // write-combined.
 int cell_grid(smore_ctx* c, const EdgeArgs& a, int k) {
-    int grid = edge_grid(c, a);
+    int grid = edge_grid(c, UpdateFamily::Cpp, a);
     const auto& B = c->blk;
     if (a.mode == SMORE_SERIAL || (size_t)k >= B.pmax_c.size()) return grid;
     // LINE-2 cells: the one-GPU launch's Hogwild concurrency cap (train.cpp
@@ -686,7 +686,7 @@ int smore_block_train_edges_async(smore_ctx* c, int block, uint64_t begin, uint6
         ak.count = n;
         ak.rec = c->d_rec;
         HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long), c->stream));
-        HIPCHK(c, launch_edge_train(ak, grid, c->stream));
+        HIPCHK(c, launch_update(update_kernel(UpdateFamily::Cpp, ak), ak, grid, c->stream));
         HIPCHK(c, hipEventRecord(c->phase_ev[2 * k + 2], c->stream));
     }
     return finish_timed(c, mode, nch);
@@ -773,7 +773,7 @@ int smore_block_train_walks_part_async(smore_ctx* c, int block, int part, int pa
     a.part_n = (uint32_t)parts;
     const int grid = B.mode == SMORE_SERIAL ? 1 : cell_grid(c, a, block);
     HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long), c->stream));
-    HIPCHK(c, launch_edge_train(a, grid, c->stream));
+    HIPCHK(c, launch_update(update_kernel(UpdateFamily::Cpp, a), a, grid, c->stream));
     return SMORE_OK;
 }
 

@@ -25,9 +25,6 @@
 
 namespace smore {
 
-enum { MODE_STORE = 0, MODE_ATOMIC = 1, MODE_HYBRID = 3 };
-
-
 // minimum waves per SIMD the register allocator must allow, per scatter mode
 // (0 = compiler default); overridable at build time for tuning.
 #ifndef SMORE_WAVES_STORE
@@ -976,12 +973,5 @@ pair_train_kernel(EdgeArgs a) {
         }
     }
 }
-
-// ---------------------------------------------------------------- dispatch
-// (G, M) pairs for dpad in [4, 512]: G = min(64, pow2ceil(dpad / 4)) lanes,
-// M = 4 * ceil(dpad / 4 / G) registers (train_kernels.h lanes_of / regs_of;
-// oracle orc_lane_width).
-#define SMORE_FOR_EACH_GM(X) \
-    X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
 
 }  // namespace smore

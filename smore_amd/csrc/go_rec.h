@@ -494,74 +494,26 @@ go_pair_kernel(EdgeArgs a) {
     }
 }
 
+// the (G, M) ladders; a unit (train_go_rec_<s|a|h>.hip) exports them as its
+// update_symbol specialisations (train_kernels.h SMORE_UPDATE_INST)
 template <int KMAX, int MODE>
-struct GoPairInst {
-    static hipError_t launch(const EdgeArgs& a, int grid, hipStream_t st) {
-        const int G = lanes_of(a.dpad), M = regs_of(a.dpad);
-#define X(g, m)                                                                          \
-    if (G == g && M == m) {                                                              \
-        hipLaunchKernelGGL((go_pair_kernel<g, m, KMAX, MODE>), dim3(grid), dim3(256),              \
-                           sh_lds_bytes(MODE == MODE_HYBRID ? a.sh_rows : 0, a.dpad), st, a);    \
-        return hipGetLastError();                                                        \
-    }
-        SMORE_FOR_EACH_GM(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-    static const void* symbol(const EdgeArgs& a) {
-        const int G = lanes_of(a.dpad), M = regs_of(a.dpad);
-#define X(g, m) \
-    if (G == g && M == m) return (const void*)go_pair_kernel<g, m, KMAX, MODE>;
-        SMORE_FOR_EACH_GM(X)
-#undef X
-        return nullptr;
-    }
-};
-
-template <int KMAX, int MODE>
-struct GoRecInst {
-    static hipError_t launch(const EdgeArgs& a, int grid, hipStream_t st) {
-        const int G = lanes_of(a.dpad), M = regs_of(a.dpad);
-        const size_t lds = MODE == MODE_HYBRID ? sh_lds_bytes(a.sh_rows, a.dpad) : 0;
-#define X(g, m)                                                                                  \
-    if (G == g && M == m) {                                                                      \
-        hipLaunchKernelGGL((go_rec_kernel<g, m, KMAX, MODE>), dim3(grid), dim3(256), lds, st, a); \
-        return hipGetLastError();                                                                \
-    }
-        SMORE_FOR_EACH_GM(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-    static const void* symbol(const EdgeArgs& a) {
-        const int G = lanes_of(a.dpad), M = regs_of(a.dpad);
+const void* go_rec_symbol(int dpad, int) {
+    const int G = lanes_of(dpad), M = regs_of(dpad);
 #define X(g, m) \
     if (G == g && M == m) return (const void*)go_rec_kernel<g, m, KMAX, MODE>;
-        SMORE_FOR_EACH_GM(X)
+    SMORE_FOR_EACH_GM(X)
 #undef X
-        return nullptr;
-    }
-};
+    return nullptr;
+}
+
+template <int KMAX, int MODE>
+const void* go_pair_symbol(int dpad, int) {
+    const int G = lanes_of(dpad), M = regs_of(dpad);
+#define X(g, m) \
+    if (G == g && M == m) return (const void*)go_pair_kernel<g, m, KMAX, MODE>;
+    SMORE_FOR_EACH_GM(X)
+#undef X
+    return nullptr;
+}
 
 }  // namespace smore
-
-// defines launch_go_rec_<name>(a, grid, st) and go_rec_symbol_<name>(a)
-#define SMORE_GO_REC_INST(name, MODE)                                                           \
-    namespace smore {                                                                           \
-    hipError_t launch_go_rec_##name(const EdgeArgs& a, int grid, hipStream_t st) {              \
-        return a.K <= 5 ? GoRecInst<5, MODE>::launch(a, grid, st) : GoRecInst<10, MODE>::launch(a, grid, st); \
-    }                                                                                           \
-    const void* go_rec_symbol_##name(const EdgeArgs& a) {                                       \
-        return a.K <= 5 ? GoRecInst<5, MODE>::symbol(a) : GoRecInst<10, MODE>::symbol(a);        \
-    }                                                                                           \
-    }
-
-// defines launch_go_pair_<name>(a, grid, st) and go_pair_symbol_<name>(a)
-#define SMORE_GO_PAIR_INST(name, MODE)                                                          \
-    namespace smore {                                                                           \
-    hipError_t launch_go_pair_##name(const EdgeArgs& a, int grid, hipStream_t st) {             \
-        return a.K <= 5 ? GoPairInst<5, MODE>::launch(a, grid, st) : GoPairInst<10, MODE>::launch(a, grid, st); \
-    }                                                                                           \
-    const void* go_pair_symbol_##name(const EdgeArgs& a) {                                      \
-        return a.K <= 5 ? GoPairInst<5, MODE>::symbol(a) : GoPairInst<10, MODE>::symbol(a);      \
-    }                                                                                           \
-    }

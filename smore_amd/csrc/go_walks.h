@@ -1,6 +1,6 @@
 // go_walks.h -- Go CTDNE's temporal walk (internal/models/ctdne/ctdne.go,
-// pkg/temporal/temporal_graph.go): device arrays and launchers shared by the
-// C ABI (train.cpp) and train_go.hip.
+// pkg/temporal/temporal_graph.go) and the Go walks' pair records: device
+// arrays and launchers shared by the C ABI (train.cpp) and train_go.hip.
 #pragma once
 #include "train_kernels.h"
 
@@ -25,13 +25,7 @@ hipError_t launch_go_pair_count(const WalkArgs& w, uint32_t* count, hipStream_t 
 // tagged: the context and negative ids carry the C hot map's bit 30 (hybrid)
 hipError_t launch_go_pair_emit(const DevGraph& g, const WalkArgs& w, uint64_t seed, int K, double alpha0,
                                const uint64_t* off, int32_t* rec, int tagged, hipStream_t st);
-// Go UpdatePair over pair records (go_rec.h go_pair_kernel; train_go_rec_*.hip):
-// mode 2 serial (the Go loop's order), 1 atomic, 0 plain stores, 3 hybrid
-hipError_t launch_go_pair_s(const EdgeArgs& a, int grid, hipStream_t st);
-hipError_t launch_go_pair_a(const EdgeArgs& a, int grid, hipStream_t st);
-hipError_t launch_go_pair_h(const EdgeArgs& a, int grid, hipStream_t st);
-const void* go_pair_symbol_s(const EdgeArgs& a);
-const void* go_pair_symbol_a(const EdgeArgs& a);
-const void* go_pair_symbol_h(const EdgeArgs& a);
+// (Go UpdatePair over these records: go_rec.h go_pair_kernel, launched as
+// train_kernels.h UpdateFamily::GoPair)
 
 }  // namespace smore

@@ -15,31 +15,10 @@ using namespace smore_host;
 
 namespace smore_host {
 
-static const void* go_rec_symbol(const EdgeArgs& a) {
-    return a.mode == SMORE_ATOMIC ? go_rec_symbol_a(a) : a.mode == SMORE_HYBRID ? go_rec_symbol_h(a) : go_rec_symbol_s(a);
-}
-
-static hipError_t launch_go_rec(const EdgeArgs& a, int grid, hipStream_t st) {
-    return a.mode == SMORE_ATOMIC   ? launch_go_rec_a(a, grid, st)
-           : a.mode == SMORE_HYBRID ? launch_go_rec_h(a, grid, st)
-                                    : launch_go_rec_s(a, grid, st);
-}
-
-// kind: 0 the C++ edge/pair kernel, 1 Go records (go_rec_kernel), 2 Go walk
-// pairs (go_pair_kernel), 3 WARP (warp_train_kernel)
-int edge_grid(smore_ctx* c, const EdgeArgs& a, bool leave_slot, int kind) {
-    if (a.mode == SMORE_SERIAL) return 1;
+int edge_grid(smore_ctx* c, const UpdateKernel& k, int mode, uint64_t count, bool leave_slot) {
+    if (mode == SMORE_SERIAL) return 1;
     int per_cu = 0;
-    const void* sym = kind == 1   ? go_rec_symbol(a)
-                      : kind == 2 ? (a.mode == SMORE_ATOMIC   ? go_pair_symbol_a(a)
-                                     : a.mode == SMORE_HYBRID ? go_pair_symbol_h(a)
-                                                              : go_pair_symbol_s(a))
-                      : kind == 3 ? (a.mode == SMORE_ATOMIC ? warp_symbol_a(a.dpad) : warp_symbol_s(a.dpad))
-                                  : edge_kernel_symbol(a);
-    if (!sym ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sym, 256, sh_lds_bytes(a.sh_rows, a.dpad)) !=
-            hipSuccess ||
-        per_cu < 1)
+    if (!k.fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, 256, k.lds) != hipSuccess || per_cu < 1)
         per_cu = 1;
     // leave one block slot per CU to the concurrent draw kernel (measured at C4:
     // 3 of 4 update blocks per CU run the update as fast as 4)
@@ -55,9 +34,9 @@ int edge_grid(smore_ctx* c, const EdgeArgs& a, bool leave_slot, int kind) {
         const int64_t cap = atoll(e);
         if (cap > 0 && cap < grid) grid = cap;
     }
-    const int G = lanes_of(a.dpad);
+    const int G = lanes_of(c->dpad);
     const int64_t groups_per_block = 256 / G;
-    const int64_t need = ((int64_t)a.count + groups_per_block - 1) / groups_per_block;
+    const int64_t need = ((int64_t)count + groups_per_block - 1) / groups_per_block;
     if (need < grid) grid = need;
     // Hogwild concurrency cap: at most V/16 resident sample groups (each keeps
     // two samples in flight), so that on small graphs the expected number of
@@ -94,10 +73,10 @@ EdgeArgs record_args(smore_ctx* c, int model, int K, int mode) {
     return a;
 }
 
-int plan_record_launch(smore_ctx* c, EdgeArgs& a, bool combine, int kind, int hot_model, double tau_default,
+int plan_record_launch(smore_ctx* c, EdgeArgs& a, bool combine, UpdateFamily f, int hot_model, double tau_default,
                        int flush_max, int* grid) {
     a.sh_rows = combine ? std::min(c->sh_max, sh_rows_max(c->dpad)) : 0;   // LDS bound for the grid
-    *grid = edge_grid(c, a, false, kind);
+    *grid = edge_grid(c, f, a);
     if (a.mode == SMORE_HYBRID) {
         const int64_t M = (int64_t)*grid * (256 / lanes_of(c->dpad));
         int rc;
@@ -112,16 +91,30 @@ int plan_record_launch(smore_ctx* c, EdgeArgs& a, bool combine, int kind, int ho
     return SMORE_OK;
 }
 
-int launch_record_update(smore_ctx* c, const EdgeArgs& ak, int grid, bool go_pairs) {
+int plan_pair_records(smore_ctx* c, UpdateFamily f, int K, int mode, uint64_t total, uint64_t seed, double alpha0,
+                      double reg, uint64_t max_records, EdgeArgs* a, int* grid) {
+    *a = record_args(c, SMORE_LINE2, K, mode);
+    a->total = total;
+    a->seed = seed;
+    a->alpha0 = alpha0;
+    a->reg = (float)reg;
+    a->alpha_rec = 1;
+    a->count = max_records;   // the grid for the most records a chunk can have
+    int rc;
+    if ((rc = plan_record_launch(c, *a, mode == SMORE_HYBRID, f, SMORE_LINE2, HOT_TAU_WALK, PAIR_FLUSH_MAX, grid)))
+        return rc;
+    a->g = dev_graph(c);   // the tables as the hot maps left them
+    a->rec = c->d_rec;
+    return SMORE_OK;
+}
+
+int launch_record_update(smore_ctx* c, UpdateFamily f, const EdgeArgs& ak, int grid) {
     HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long), c->stream));
     const int g = ak.mode == SMORE_SERIAL ? 1 : grid;
     if (c->census)
         HIPCHK(c, launch_row_census(ak.rec, ak.count, ak.count_dev, rec_width(kmax_of(ak.K)), ak.K, c->d_census[0],
                                     c->d_census[1], c->cus, c->stream));
-    else if (!go_pairs) HIPCHK(c, launch_edge_train(ak, g, c->stream));
-    else if (ak.mode == SMORE_ATOMIC) HIPCHK(c, launch_go_pair_a(ak, g, c->stream));
-    else if (ak.mode == SMORE_HYBRID) HIPCHK(c, launch_go_pair_h(ak, g, c->stream));
-    else HIPCHK(c, launch_go_pair_s(ak, g, c->stream));
+    else HIPCHK(c, launch_update(update_kernel(f, ak), ak, g, c->stream));
     return SMORE_OK;
 }
 
@@ -143,15 +136,13 @@ int sync_after(smore_ctx* c, int rc, bool check_last_error) {
 }  // namespace smore_host
 
 // the hot/cold record split of the C++ edge models' hybrid scatter (train_draw.hip
-// draw_split_kernel): SMORE_SPLIT=1 / 0 overrides the per-model default
-static bool split_on(int model) {
+// draw_split_kernel): off unless SMORE_SPLIT is set to a non-zero number
+static bool split_on() {
     static const int env = [] {
         const char* e = getenv("SMORE_SPLIT");
         return e ? atoi(e) : -1;
     }();
-    if (env >= 0) return env != 0;
-    (void)model;
-    return false;
+    return env > 0;
 }
 
 extern "C" {
@@ -181,6 +172,7 @@ int smore_train_edges_async(smore_ctx* c, int model, uint64_t begin, uint64_t co
     // (go_draw_kernel) and the Go rules on them (go_rec.h), with every
     // scatter mode; BPR is Go's two-table, one-negative rule
     const bool go = c->semantics == SMORE_SEM_GO;
+    const UpdateFamily fam = go ? UpdateFamily::GoRec : UpdateFamily::Cpp;
     if (go) {
         if (model == SMORE_MF) return fail(c, SMORE_EINVAL, "Go semantics has no MF model");
         if (K > 10) return fail(c, SMORE_EINVAL, "Go semantics: K <= 10");
@@ -205,7 +197,7 @@ int smore_train_edges_async(smore_ctx* c, int model, uint64_t begin, uint64_t co
         const char* e = getenv("SMORE_BPR_SCATTER");
         EdgeArgs t = a;
         t.sh_rows = 0;
-        const int64_t Mb = (int64_t)edge_grid(c, t, false, 0) * (256 / lanes_of(c->dpad));
+        const int64_t Mb = (int64_t)edge_grid(c, UpdateFamily::Cpp, t) * (256 / lanes_of(c->dpad));
         const bool small = c->hot_tau < 0 && 16.0 * (double)Mb >= (double)c->g->V;
         if (!small && !(e && !strcmp(e, "tagged"))) a.mode = mode = SMORE_HOGWILD;
     }
@@ -216,7 +208,7 @@ int smore_train_edges_async(smore_ctx* c, int model, uint64_t begin, uint64_t co
     // Go BPR has two tables (users W, items C): the LINE-2 row roles
     const int hot_model = go && model == SMORE_BPR ? SMORE_LINE2 : model;
     int grid;
-    if ((rc = plan_record_launch(c, a, combine, go ? 1 : 0, hot_model, go ? HOT_TAU_WALK : HOT_TAU_EDGE,
+    if ((rc = plan_record_launch(c, a, combine, fam, hot_model, go ? HOT_TAU_WALK : HOT_TAU_EDGE,
                                  EDGE_FLUSH_MAX, &grid)))
         return rc;
     // edge models: draw kernel -> update kernel per chunk of samples.  With
@@ -240,14 +232,14 @@ int smore_train_edges_async(smore_ctx* c, int model, uint64_t begin, uint64_t co
     const DevGraph dg = dev_graph(c);
     // hot/cold record split (C++ rules, hybrid): records touching no hot row
     // run through the plain-store kernel (train_draw.hip draw_split_kernel);
-    // SMORE_SPLIT=1/0 forces it on / off, default split_default()
-    const bool split = mode == SMORE_HYBRID && !go && dg.vt32 && split_on(model);
+    // a study path, on with SMORE_SPLIT=1
+    const bool split = mode == SMORE_HYBRID && !go && dg.vt32 && split_on();
     if (split && !c->d_split) HIPCHK(c, hipMalloc((void**)&c->d_split, 4 * sizeof(unsigned long long)));
     // tuning knob: SMORE_DRAW_LEAVE=0 keeps the update kernel's full grid
     // while the next chunk's draws run beside it
     const char* leave_env = getenv("SMORE_DRAW_LEAVE");
     const bool leave = !leave_env || atoi(leave_env) != 0;
-    const int ugrid = nch > 1 ? edge_grid(c, a, leave, go ? 1 : 0) : grid;
+    const int ugrid = nch > 1 ? edge_grid(c, fam, a, leave) : grid;
     hipStream_t ds = nch > 1 ? c->draw_stream : c->stream;
     auto recbuf = [&](int k) { return c->d_rec + (size_t)(k % nbuf) * chunk * RW; };
     auto draw = [&](int k) -> int {
@@ -278,22 +270,21 @@ int smore_train_edges_async(smore_ctx* c, int model, uint64_t begin, uint64_t co
         ak.count = n;
         ak.rec = recbuf(k);
         HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long), c->stream));
-        if (go) HIPCHK(c, launch_go_rec(ak, ugrid, c->stream));
-        else if (split) {
+        if (split) {
             // hot records [0, h) on the hybrid kernel, cold [h, n) on the
             // plain-store kernel; both read their rate from the record
             unsigned long long* cnt = c->d_split + 2 * (k % nbuf);
             ak.alpha_rec = 2;
             ak.count_dev = reinterpret_cast<const uint64_t*>(cnt);
-            HIPCHK(c, launch_edge_train(ak, ugrid, c->stream));
+            HIPCHK(c, launch_update(update_kernel(fam, ak), ak, ugrid, c->stream));
             EdgeArgs ac = ak;
             ac.mode = SMORE_HOGWILD;
             ac.sh_rows = 0;
             ac.count_dev = nullptr;
             ac.rec_base = reinterpret_cast<const uint64_t*>(cnt);
             HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long), c->stream));
-            HIPCHK(c, launch_edge_train(ac, edge_grid(c, ac), c->stream));
-        } else HIPCHK(c, launch_edge_train(ak, ugrid, c->stream));
+            HIPCHK(c, launch_update(update_kernel(fam, ac), ac, edge_grid(c, fam, ac), c->stream));
+        } else HIPCHK(c, launch_update(update_kernel(fam, ak), ak, ugrid, c->stream));
         HIPCHK(c, hipEventRecord(c->phase_ev[2 * k + 2], c->stream));
         HIPCHK(c, hipEventRecord(c->sync_ev[2 * k + 1], c->stream));
     }
@@ -429,7 +420,6 @@ static int train_walks(smore_ctx* c, int rule, uint64_t walk_begin, uint64_t wal
     a.alpha0 = alpha0;
     // Go walks on a unit-weight graph: O(1) CDF target (go_target, tcum null)
     if (go && c->go_unit_w) a.tcum = nullptr;
-    EdgeArgs ar = a;   // the update kernel over pair records
     if (c->pair_walks < chunk + 1) {
         dfree(c->d_pcount);
         dfree(c->d_poff);
@@ -439,13 +429,13 @@ static int train_walks(smore_ctx* c, int rule, uint64_t walk_begin, uint64_t wal
         c->pair_walks = chunk + 1;
     }
     if ((rc = ensure_cap(c, c->d_rec, c->rec_cap, (size_t)(chunk * pb * RW)))) return rc;
-    ar.alpha_rec = 1;
-    ar.count = chunk * pb;   // grid for the most pairs a chunk can have
+    // the update kernel over pair records; a stays the walk kernel's, taken
+    // before the hot maps
+    const UpdateFamily fam = go ? UpdateFamily::GoPair : UpdateFamily::Cpp;
+    EdgeArgs ar;
     int ugrid;
-    if ((rc = plan_record_launch(c, ar, mode == SMORE_HYBRID, go ? 2 : 0, SMORE_LINE2, HOT_TAU_WALK, PAIR_FLUSH_MAX,
-                                 &ugrid)))
-        return rc;
-    ar.g = dev_graph(c);   // the tables as the hot maps left them
+    if ((rc = plan_pair_records(c, fam, K, mode, total, seed, alpha0, 0.0, chunk * pb, &ar, &ugrid))) return rc;
+    ar.tcum = a.tcum;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     for (uint64_t b = walk_begin; b < walk_end; b += chunk) {
         WalkArgs w;
@@ -500,8 +490,7 @@ static int train_walks(smore_ctx* c, int rule, uint64_t walk_begin, uint64_t wal
         ak.begin = 0;
         ak.count = w.nwalks * pb;
         ak.count_dev = c->d_poff + w.nwalks;
-        ak.rec = c->d_rec;
-        if ((rc = launch_record_update(c, ak, ugrid, go))) return rc;
+        if ((rc = launch_record_update(c, fam, ak, ugrid))) return rc;
     }
     return finish_timed(c, mode, 0);
 }
@@ -621,17 +610,9 @@ int smore_train_app_async(smore_ctx* c, uint64_t unit_begin, uint64_t unit_end, 
     const int RW = rec_width(kmax_of(K));
     const uint64_t chunk = std::min<uint64_t>(unit_end - unit_begin, (uint64_t)1 << 25);
     if ((rc = ensure_cap(c, c->d_rec, c->rec_cap, (size_t)(chunk * RW)))) return rc;
-    EdgeArgs a = record_args(c, SMORE_LINE2, K, mode);
-    a.total = total;
-    a.seed = seed;
-    a.alpha0 = alpha0;
-    a.alpha_rec = 1;
-    a.count = chunk;
+    EdgeArgs a;
     int grid;
-    if ((rc = plan_record_launch(c, a, mode == SMORE_HYBRID, 0, SMORE_LINE2, HOT_TAU_WALK, PAIR_FLUSH_MAX, &grid)))
-        return rc;
-    a.g = dev_graph(c);   // the tables as the hot maps left them
-    a.rec = c->d_rec;
+    if ((rc = plan_pair_records(c, UpdateFamily::Cpp, K, mode, total, seed, alpha0, 0.0, chunk, &a, &grid))) return rc;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     for (uint64_t b = unit_begin; b < unit_end; b += chunk) {
         AppArgs p;
@@ -646,7 +627,7 @@ int smore_train_app_async(smore_ctx* c, uint64_t unit_begin, uint64_t unit_end, 
         EdgeArgs ak = a;
         ak.begin = 0;
         ak.count = p.n;
-        if ((rc = launch_record_update(c, ak, grid, false))) return rc;
+        if ((rc = launch_record_update(c, UpdateFamily::Cpp, ak, grid))) return rc;
     }
     return finish_timed(c, mode, 0);
 }
@@ -673,18 +654,10 @@ int smore_train_hpe_async(smore_ctx* c, uint64_t begin, uint64_t count, uint64_t
     const uint64_t nrec = (uint64_t)walk_steps + 1;
     const uint64_t chunk = std::min<uint64_t>(count, std::max<uint64_t>(1, ((uint64_t)1 << 27) / nrec));
     if ((rc = ensure_cap(c, c->d_rec, c->rec_cap, (size_t)(chunk * nrec * RW)))) return rc;
-    EdgeArgs a = record_args(c, SMORE_LINE2, K, mode);
-    a.total = total;
-    a.seed = seed;
-    a.alpha0 = alpha0;
-    a.reg = (float)reg;
-    a.alpha_rec = 1;
-    a.count = chunk * nrec;
+    EdgeArgs a;
     int grid;
-    if ((rc = plan_record_launch(c, a, mode == SMORE_HYBRID, 0, SMORE_LINE2, HOT_TAU_WALK, PAIR_FLUSH_MAX, &grid)))
+    if ((rc = plan_pair_records(c, UpdateFamily::Cpp, K, mode, total, seed, alpha0, reg, chunk * nrec, &a, &grid)))
         return rc;
-    a.g = dev_graph(c);   // the tables as the hot maps left them
-    a.rec = c->d_rec;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     for (uint64_t b = begin; b < begin + count; b += chunk) {
         HpeArgs p;
@@ -696,7 +669,7 @@ int smore_train_hpe_async(smore_ctx* c, uint64_t begin, uint64_t count, uint64_t
         EdgeArgs ak = a;
         ak.begin = 0;
         ak.count = p.n * nrec;
-        if ((rc = launch_record_update(c, ak, grid, false))) return rc;
+        if ((rc = launch_record_update(c, UpdateFamily::Cpp, ak, grid))) return rc;
     }
     return finish_timed(c, mode, 0);
 }
@@ -743,18 +716,10 @@ int smore_host::train_pairs_core(smore_ctx* c, const int32_t* v, const int32_t* 
     // either buffer: growing frees it, and the free waits for the device
     if ((rc = ensure_cap(c, c->d_pairs, c->pairs_cap, (size_t)(2 * chunk)))) return rc;
     if ((rc = ensure_cap(c, c->d_rec, c->rec_cap, (size_t)(chunk * RW)))) return rc;
-    EdgeArgs a = record_args(c, SMORE_LINE2, K, mode);
-    a.total = 1;
-    a.seed = seed;
-    a.alpha0 = alpha;
-    a.alpha_rec = 1;
-    a.count = chunk;
+    const UpdateFamily fam = go ? UpdateFamily::GoPair : UpdateFamily::Cpp;
+    EdgeArgs a;
     int grid;
-    if ((rc = plan_record_launch(c, a, mode == SMORE_HYBRID, go ? 2 : 0, SMORE_LINE2, HOT_TAU_WALK, PAIR_FLUSH_MAX,
-                                 &grid)))
-        return rc;
-    a.g = dev_graph(c);   // the tables as the hot maps left them
-    a.rec = c->d_rec;
+    if ((rc = plan_pair_records(c, fam, K, mode, 1, seed, alpha, 0.0, chunk, &a, &grid))) return rc;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     for (uint64_t b = 0; b < (uint64_t)n; b += chunk) {
         const uint64_t m = std::min<uint64_t>(chunk, (uint64_t)n - b);
@@ -772,7 +737,7 @@ int smore_host::train_pairs_core(smore_ctx* c, const int32_t* v, const int32_t* 
         // CH_ROUNDS-record slices keep W_v in registers over a long batch
         const uint64_t groups = (uint64_t)grid * (uint64_t)(256 / lanes_of(c->dpad));
         if (m < groups * CH_ROUNDS) ak.pair_slice = (uint32_t)std::max<uint64_t>(1, (m + groups - 1) / groups);
-        if ((rc = launch_record_update(c, ak, grid, go))) return rc;
+        if ((rc = launch_record_update(c, fam, ak, grid))) return rc;
     }
     return finish_timed(c, mode, 0);
 }

@@ -1,3 +1,3 @@
 // edge_train_kernel instantiations: atomic scatter, up to 20 negatives (edge_inst.h)
 #include "edge_inst.h"
-SMORE_EDGE_INST(a20, 20, smore::MODE_ATOMIC)
+SMORE_UPDATE_INST(Edge, smore::MODE_ATOMIC, 20, edge_symbol)

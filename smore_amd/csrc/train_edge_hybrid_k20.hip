@@ -1,3 +1,3 @@
 // edge_train_kernel instantiations: hybrid scatter, up to 20 negatives (edge_inst.h)
 #include "edge_inst.h"
-SMORE_EDGE_INST(h20, 20, smore::MODE_HYBRID)
+SMORE_UPDATE_INST(Edge, smore::MODE_HYBRID, 20, edge_symbol)

@@ -1,5 +1,6 @@
-// go_rec_kernel instantiations (go_rec.h): MODE_HYBRID scatter, KMAX 5 and 10
+// go_rec_kernel instantiations (go_rec.h): MODE_HYBRID scatter, KMAX 5 and 10; the Go walk-pair kernel likewise
 #include "go_rec.h"
-#include "go_walks.h"
-SMORE_GO_REC_INST(h, smore::MODE_HYBRID)
-SMORE_GO_PAIR_INST(h, smore::MODE_HYBRID)
+SMORE_UPDATE_INST(GoRec, smore::MODE_HYBRID, 5, go_rec_symbol)
+SMORE_UPDATE_INST(GoRec, smore::MODE_HYBRID, 10, go_rec_symbol)
+SMORE_UPDATE_INST(GoPair, smore::MODE_HYBRID, 5, go_pair_symbol)
+SMORE_UPDATE_INST(GoPair, smore::MODE_HYBRID, 10, go_pair_symbol)

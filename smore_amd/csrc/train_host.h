@@ -79,9 +79,13 @@ int build_hot_maps(smore_ctx* c, int model, int K, int64_t M, double tau_default
 int ensure_packed(smore_ctx* c);
 
 // ---------------------------------------------------------------- train.cpp
-// the update launch's grid.  kind: 0 the C++ edge/pair kernel, 1 Go records
-// (go_rec_kernel), 2 Go walk pairs (go_pair_kernel), 3 WARP (warp_train_kernel)
-int edge_grid(smore_ctx* c, const EdgeArgs& a, bool leave_slot = false, int kind = 0);
+// the grid of an update launch of up to `count` records through kernel k
+// (train_kernels.h update_kernel) in scatter `mode`: what the occupancy of k
+// allows, under the knobs' and the small-graph caps
+int edge_grid(smore_ctx* c, const UpdateKernel& k, int mode, uint64_t count, bool leave_slot = false);
+inline int edge_grid(smore_ctx* c, UpdateFamily f, const EdgeArgs& a, bool leave_slot = false) {
+    return edge_grid(c, update_kernel(f, a), a.mode, a.count, leave_slot);
+}
 int grow_events(smore_ctx* c, std::vector<hipEvent_t>& v, size_t n);
 // the update-kernel arguments every record path fills alike (the tables by
 // the model's row roles); the caller adds its own
@@ -89,11 +93,17 @@ EdgeArgs record_args(smore_ctx* c, int model, int K, int mode);
 // the launch plan of a record path whose a.count bounds a chunk's records:
 // the grid (LDS sized for the most write-combined rows), the hot maps of a
 // hybrid launch for that grid, then the write-combined set they chose in a
-int plan_record_launch(smore_ctx* c, EdgeArgs& a, bool combine, int kind, int hot_model, double tau_default,
+int plan_record_launch(smore_ctx* c, EdgeArgs& a, bool combine, UpdateFamily f, int hot_model, double tau_default,
                        int flush_max, int* grid);
-// one chunk of pair records through the update kernel of the mode (the row
-// census instead while one is in progress); go_pairs: the Go UpdatePair kernels
-int launch_record_update(smore_ctx* c, const EdgeArgs& ak, int grid, bool go_pairs);
+// the plan of the drivers whose records are LINE-2 pairs with the rate in the
+// record (walks, APP, HPE, caller pairs): the arguments (at most max_records
+// per chunk, in c->d_rec, sized by the caller before) and the grid, the
+// tables as the hot maps left them
+int plan_pair_records(smore_ctx* c, UpdateFamily f, int K, int mode, uint64_t total, uint64_t seed, double alpha0,
+                      double reg, uint64_t max_records, EdgeArgs* a, int* grid);
+// one chunk of pair records through the family's update kernel of the mode
+// (the row census instead while one is in progress)
+int launch_record_update(smore_ctx* c, UpdateFamily f, const EdgeArgs& ak, int grid);
 int finish_timed(smore_ctx* c, int mode, int phase_n);
 // a blocking wrapper's tail: the async call's rc, or the stream's completion
 int sync_after(smore_ctx* c, int rc, bool check_last_error = false);

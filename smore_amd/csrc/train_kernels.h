@@ -5,9 +5,14 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "../../include/smore_hip.h"
 #include "device_common.h"
 
 namespace smore {
+
+// scatter of an update-kernel instantiation (template parameter MODE); a
+// SMORE_SERIAL call runs the MODE_STORE instantiation with one sample group
+enum { MODE_STORE = SMORE_HOGWILD, MODE_ATOMIC = SMORE_ATOMIC, MODE_HYBRID = SMORE_HYBRID };
 
 struct EdgeArgs {
     DevGraph g;
@@ -172,14 +177,9 @@ inline size_t sh_lds_bytes(int sh_rows, int dpad) {
 }
 inline uint32_t sh_hash_of(int32_t id) { return ((uint32_t)id * 2654435761u) >> 24; }
 // Go edge models on records: go_draw_kernel (train_go.hip; unit_w: every edge
-// weight is 1) then go_rec_kernel (go_rec.h; train_go_rec_<mode>.hip)
+// weight is 1) then go_rec_kernel (go_rec.h; UpdateFamily::GoRec)
 hipError_t launch_go_draw(const DevGraph& g, const double* tcum, int unit_w, uint64_t seed, uint64_t begin,
                           uint64_t count, int K, int32_t* rec, unsigned long long* skipped, hipStream_t st);
-#define SMORE_DECL_GO_REC(name)                                                  \
-    hipError_t launch_go_rec_##name(const EdgeArgs& a, int grid, hipStream_t st); \
-    const void* go_rec_symbol_##name(const EdgeArgs& a);
-SMORE_DECL_GO_REC(s) SMORE_DECL_GO_REC(a) SMORE_DECL_GO_REC(h)
-#undef SMORE_DECL_GO_REC
 hipError_t launch_go_walk(const EdgeArgs& a, const WalkArgs& w, int grid, hipStream_t st);
 hipError_t launch_go_sample(const DevGraph& g, const double* tcum, uint64_t seed, uint64_t begin, uint64_t count,
                             int K, int32_t* out, hipStream_t st);
@@ -205,30 +205,11 @@ hipError_t launch_caller_pairs(const DevGraph& g, const int32_t* pv, const int32
 // samples and finished walks) count nothing.  count_dev: the count on the device
 hipError_t launch_row_census(const int32_t* rec, uint64_t n, const uint64_t* count_dev, int RW, int K,
                              unsigned long long* cw, unsigned long long* cc, int cus, hipStream_t st);
-// edge kernel instantiations, one per (scatter mode s/a/h, KMAX) (train_edge_*.hip)
-#define SMORE_DECL_EDGE(name)                                                   \
-    hipError_t launch_edge_##name(const EdgeArgs& a, int grid, hipStream_t st); \
-    const void* edge_symbol_##name(const EdgeArgs& a);
-SMORE_DECL_EDGE(s5) SMORE_DECL_EDGE(s10) SMORE_DECL_EDGE(s20)
-SMORE_DECL_EDGE(a5) SMORE_DECL_EDGE(a10) SMORE_DECL_EDGE(a20)
-SMORE_DECL_EDGE(h5) SMORE_DECL_EDGE(h10) SMORE_DECL_EDGE(h20)
-// DeepWalk pair-kernel instantiations (train_pair_*.hip; K <= 10)
-#define SMORE_DECL_PAIR(name)                                                   \
-    hipError_t launch_pair_##name(const EdgeArgs& a, int grid, hipStream_t st); \
-    const void* pair_symbol_##name(const EdgeArgs& a);
-SMORE_DECL_PAIR(s5) SMORE_DECL_PAIR(s10) SMORE_DECL_PAIR(a5) SMORE_DECL_PAIR(a10)
-SMORE_DECL_PAIR(h5) SMORE_DECL_PAIR(h10)
-#undef SMORE_DECL_PAIR
-#undef SMORE_DECL_EDGE
-// launch_edge_train / edge_kernel_symbol route DeepWalk pair records
-// (alpha_rec) in the Hogwild modes to pair_train_kernel
-hipError_t launch_edge_train(const EdgeArgs& a, int grid, hipStream_t st);
-const void* edge_kernel_symbol(const EdgeArgs& a);
 // WARP (warp_kernels.h; train_warp_<s|a>.hip): the update kernel draws the
 // negatives of trials 1..31 itself
 constexpr int WARP_TRIALS = 32;              // src/proNet.cpp:1366
 constexpr int WARP_KMAX = 5;                 // record width of the K = 1 draw
-enum { WARP_STORE = 0, WARP_ATOMIC = 1 };
+enum { WARP_STORE = MODE_STORE, WARP_ATOMIC = MODE_ATOMIC };
 
 struct WarpArgs {
     DevGraph g;
@@ -243,11 +224,82 @@ struct WarpArgs {
     int groups;                    // sample groups of a block that take samples (<= 256 / G; the rest idle)
 };
 
-// launch and occupancy symbol per scatter (train_warp_<s|a>.hip)
-hipError_t launch_warp_s(const WarpArgs& a, int grid, hipStream_t st);
-hipError_t launch_warp_a(const WarpArgs& a, int grid, hipStream_t st);
-const void* warp_symbol_s(int dpad);
-const void* warp_symbol_a(int dpad);
+// ---------------------------------------------------------------- update kernels
+// The kernels that turn records into row updates: edge_train_kernel and
+// pair_train_kernel (edge_kernels.h), go_rec_kernel and go_pair_kernel
+// (go_rec.h), warp_train_kernel (warp_kernels.h).  Each takes its argument
+// struct as its one by-value parameter and exists per scatter MODE, KMAX
+// bucket and (G, M) lane layout.
+
+// (G, M) pairs for dpad in [4, 512]: G = min(64, pow2ceil(dpad / 4)) lanes,
+// M = 4 * ceil(dpad / 4 / G) registers (lanes_of / regs_of; oracle
+// orc_lane_width)
+#define SMORE_FOR_EACH_GM(X) \
+    X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
+
+enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp };
+
+// Every (family, MODE, KMAX) instantiation.  Each is built in a unit of its
+// own (train_edge_<mode>_k<KMAX>.hip, train_pair_<s|a|h><KMAX>.hip,
+// train_warp_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a mode's four Go ones),
+// so a new bucket is one line here and its .hip file.
+#define SMORE_FOR_EACH_UPDATE_KERNEL(X)                                             \
+    X(Edge, MODE_STORE, 5) X(Edge, MODE_STORE, 10) X(Edge, MODE_STORE, 20)          \
+    X(Edge, MODE_ATOMIC, 5) X(Edge, MODE_ATOMIC, 10) X(Edge, MODE_ATOMIC, 20)       \
+    X(Edge, MODE_HYBRID, 5) X(Edge, MODE_HYBRID, 10) X(Edge, MODE_HYBRID, 20)       \
+    X(Pair, MODE_STORE, 5) X(Pair, MODE_STORE, 10)                                  \
+    X(Pair, MODE_ATOMIC, 5) X(Pair, MODE_ATOMIC, 10)                                \
+    X(Pair, MODE_HYBRID, 5) X(Pair, MODE_HYBRID, 10)                                \
+    X(GoRec, MODE_STORE, 5) X(GoRec, MODE_STORE, 10)                                \
+    X(GoRec, MODE_ATOMIC, 5) X(GoRec, MODE_ATOMIC, 10)                              \
+    X(GoRec, MODE_HYBRID, 5) X(GoRec, MODE_HYBRID, 10)                              \
+    X(GoPair, MODE_STORE, 5) X(GoPair, MODE_STORE, 10)                              \
+    X(GoPair, MODE_ATOMIC, 5) X(GoPair, MODE_ATOMIC, 10)                            \
+    X(GoPair, MODE_HYBRID, 5) X(GoPair, MODE_HYBRID, 10)                            \
+    X(Warp, WARP_STORE, WARP_KMAX) X(Warp, WARP_ATOMIC, WARP_KMAX)
+
+// The instantiation's kernel for dpad's lane layout (Edge: and the model's
+// rule), or nullptr when there is none: a (G, M) outside the list, BPR with
+// KMAX != 5.  Specialised by the instantiation's unit (SMORE_UPDATE_INST).
+template <KernelFamily F, int MODE, int KMAX>
+const void* update_symbol(int dpad, int model);
+#define X(F, MODE, KMAX) \
+    template <>          \
+    const void* update_symbol<KernelFamily::F, MODE, KMAX>(int dpad, int model);
+SMORE_FOR_EACH_UPDATE_KERNEL(X)
+#undef X
+// in a unit: the specialisation, from the family's (G, M) ladder
+// ladder<KMAX, MODE>(dpad, model) (edge_inst.h, go_rec.h, warp_kernels.h)
+#define SMORE_UPDATE_INST(F, MODE, KMAX, ladder)                                          \
+    namespace smore {                                                                     \
+    template <>                                                                           \
+    const void* update_symbol<KernelFamily::F, MODE, KMAX>(int dpad, int model) {         \
+        return ladder<KMAX, MODE>(dpad, model);                                           \
+    }                                                                                     \
+    }
+
+// What a driver with EdgeArgs asks for.  Cpp: pair records (alpha_rec 1) in a
+// parallel mode with K <= 10 and !rec_edge go to pair_train_kernel, everything
+// else, serial included, to edge_train_kernel.  (WARP resolves from its WarpArgs.)
+enum class UpdateFamily { Cpp, GoRec, GoPair };
+
+// a resolved kernel: fn == nullptr means no such instantiation (the launch
+// fails with hipErrorInvalidValue); lds: the dynamic LDS of a hybrid launch
+struct UpdateKernel {
+    const void* fn;
+    size_t lds;
+};
+UpdateKernel update_kernel(UpdateFamily f, const EdgeArgs& a);
+UpdateKernel update_kernel(const WarpArgs& a);
+
+// the one launch of the update kernels: 256 threads, `a` as the kernel's parameter
+template <class Args>
+hipError_t launch_update(const UpdateKernel& k, const Args& a, int grid, hipStream_t st) {
+    if (!k.fn) return hipErrorInvalidValue;
+    void* p[] = {(void*)&a};
+    (void)hipLaunchKernel(k.fn, dim3(grid), dim3(256), p, k.lds, st);
+    return hipGetLastError();
+}
 
 hipError_t launch_sample(const DevGraph& g, uint64_t seed, uint64_t begin, uint64_t count, int K,
                          int bpr, int32_t* out, hipStream_t st);

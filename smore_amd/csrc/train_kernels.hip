@@ -1,6 +1,7 @@
-// train_kernels.hip -- sampler / init kernels and the launch dispatch of the
-// sampled-SGD update kernels (edge_kernels.h; instantiated in
-// train_edge_<mode>_k<KMAX>.hip).
+// train_kernels.hip -- sampler / init kernels and the resolver of the update
+// kernels: update_kernel maps (family, scatter mode, K, dpad, model) to the
+// instantiation that one of the train_edge_* / train_pair_* / train_go_rec_*
+// / train_warp_* units exports (train_kernels.h SMORE_FOR_EACH_UPDATE_KERNEL).
 
 #include "train_kernels.h"
 
@@ -60,35 +61,39 @@ int lanes_of(int dpad) {
     return G;
 }
 
-#define SMORE_EDGE_DISPATCH(fn, ...)                                           \
-    {                                                                          \
-        const int k = kmax_of(a.K);                                            \
-        if (a.mode == 1) return k == 5 ? fn##a5(__VA_ARGS__) : k == 10 ? fn##a10(__VA_ARGS__) : fn##a20(__VA_ARGS__); \
-        if (a.mode == 3) return k == 5 ? fn##h5(__VA_ARGS__) : k == 10 ? fn##h10(__VA_ARGS__) : fn##h20(__VA_ARGS__); \
-        return k == 5 ? fn##s5(__VA_ARGS__) : k == 10 ? fn##s10(__VA_ARGS__) : fn##s20(__VA_ARGS__);                \
-    }
-
-#define SMORE_PAIR_DISPATCH(fn, ...)                                           \
-    {                                                                          \
-        const bool k5 = kmax_of(a.K) == 5;                                     \
-        if (a.mode == 1) return k5 ? fn##a5(__VA_ARGS__) : fn##a10(__VA_ARGS__); \
-        if (a.mode == 3) return k5 ? fn##h5(__VA_ARGS__) : fn##h10(__VA_ARGS__); \
-        return k5 ? fn##s5(__VA_ARGS__) : fn##s10(__VA_ARGS__);                \
-    }
-
-static bool pair_path(const EdgeArgs& a) { return a.alpha_rec == 1 && a.mode != 2 && a.K <= 10 && !a.rec_edge; }
-
-hipError_t launch_edge_train(const EdgeArgs& a, int grid, hipStream_t st) {
-    if (pair_path(a)) SMORE_PAIR_DISPATCH(launch_pair_, a, grid, st)
-    SMORE_EDGE_DISPATCH(launch_edge_, a, grid, st)
+// the instantiation (family, scatter of `mode`, kmax) for dpad and model
+static const void* find_symbol(KernelFamily f, int mode, int kmax, int dpad, int model) {
+    const int inst = mode == SMORE_ATOMIC ? MODE_ATOMIC : mode == SMORE_HYBRID ? MODE_HYBRID : MODE_STORE;
+#define X(F, MODE, KMAX)                                         \
+    if (f == KernelFamily::F && inst == MODE && kmax == KMAX)    \
+        return update_symbol<KernelFamily::F, MODE, KMAX>(dpad, model);
+    SMORE_FOR_EACH_UPDATE_KERNEL(X)
+#undef X
+    return nullptr;
 }
 
-const void* edge_kernel_symbol(const EdgeArgs& a) {
-    if (pair_path(a)) SMORE_PAIR_DISPATCH(pair_symbol_, a)
-    SMORE_EDGE_DISPATCH(edge_symbol_, a)
+static bool pair_path(const EdgeArgs& a) {
+    return a.alpha_rec == 1 && a.mode != SMORE_SERIAL && a.K <= 10 && !a.rec_edge;
 }
-#undef SMORE_EDGE_DISPATCH
-#undef SMORE_PAIR_DISPATCH
+
+UpdateKernel update_kernel(UpdateFamily f, const EdgeArgs& a) {
+    KernelFamily kf = KernelFamily::Edge;
+    int kmax = kmax_of(a.K);
+    switch (f) {
+        case UpdateFamily::Cpp: kf = pair_path(a) ? KernelFamily::Pair : KernelFamily::Edge; break;
+        // the Go kernels have KMAX 5 and 10 (the drivers reject K > 10)
+        case UpdateFamily::GoRec: kf = KernelFamily::GoRec; kmax = std::min(kmax, 10); break;
+        case UpdateFamily::GoPair: kf = KernelFamily::GoPair; kmax = std::min(kmax, 10); break;
+    }
+    return {find_symbol(kf, a.mode, kmax, a.dpad, a.model),
+            a.mode == SMORE_HYBRID ? sh_lds_bytes(a.sh_rows, a.dpad) : 0};
+}
+
+// SMORE_ATOMIC runs the atomic scatter, every other mode the plain stores
+UpdateKernel update_kernel(const WarpArgs& a) {
+    const int mode = a.mode == SMORE_ATOMIC ? SMORE_ATOMIC : SMORE_HOGWILD;
+    return {find_symbol(KernelFamily::Warp, mode, WARP_KMAX, a.dpad, 0), 0};
+}
 
 hipError_t launch_sample(const DevGraph& g, uint64_t seed, uint64_t begin, uint64_t count, int K,
                          int bpr, int32_t* out, hipStream_t st) {

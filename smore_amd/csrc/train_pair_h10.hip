@@ -1,3 +1,3 @@
 // pair_train_kernel instantiations: hybrid scatter, up to 10 negatives (edge_inst.h)
 #include "edge_inst.h"
-SMORE_PAIR_INST(h10, 10, smore::MODE_HYBRID)
+SMORE_UPDATE_INST(Pair, smore::MODE_HYBRID, 10, pair_symbol)

@@ -61,10 +61,18 @@ int smore_train_warp_async(smore_ctx* c, uint64_t begin, uint64_t count, uint64_
     if (const char* e = getenv("SMORE_DRAW_CHUNK")) chunk_max = std::max<uint64_t>(1024, strtoull(e, nullptr, 10));
     const uint64_t chunk = std::min<uint64_t>(count, chunk_max);
     const int nch = (int)((count + chunk - 1) / chunk);
-    EdgeArgs e = record_args(c, SMORE_BPR, 1, run_mode);
-    e.count = chunk;
-    int grid;
-    if ((rc = plan_record_launch(c, e, false, 3, SMORE_BPR, HOT_TAU_EDGE, EDGE_FLUSH_MAX, &grid))) return rc;
+    WarpArgs a{};
+    a.sig = c->d_sig;
+    a.T = c->d_table[0];
+    a.work = c->d_work;
+    a.stats = c->d_warp_stats;
+    a.total = total;
+    a.seed = seed;
+    a.alpha0 = alpha0;
+    a.dpad = c->dpad;
+    a.mode = run_mode;
+    const UpdateKernel kern = update_kernel(a);
+    int grid = edge_grid(c, kern, run_mode, chunk);
     int groups = 256 / lanes_of(c->dpad);   // per block
     if (run_mode == SMORE_HOGWILD) {
         const int64_t cap = warp_store_groups(c);
@@ -78,18 +86,8 @@ int smore_train_warp_async(smore_ctx* c, uint64_t begin, uint64_t count, uint64_
     if ((rc = ensure_cap(c, c->d_rec, c->rec_cap, chunk * RW))) return rc;
     if ((rc = grow_events(c, c->phase_ev, 2 * (size_t)nch + 1))) return rc;
     if ((rc = ensure_packed(c))) return rc;
-    WarpArgs a{};
     a.g = dev_graph(c);
-    a.sig = c->d_sig;
-    a.T = c->d_table[0];
     a.rec = c->d_rec;
-    a.work = c->d_work;
-    a.stats = c->d_warp_stats;
-    a.total = total;
-    a.seed = seed;
-    a.alpha0 = alpha0;
-    a.dpad = c->dpad;
-    a.mode = run_mode;
     a.groups = groups;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     HIPCHK(c, hipEventRecord(c->phase_ev[0], c->stream));
@@ -100,8 +98,7 @@ int smore_train_warp_async(smore_ctx* c, uint64_t begin, uint64_t count, uint64_
         a.begin = begin + b;
         a.count = n;
         HIPCHK(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long), c->stream));
-        if (run_mode == SMORE_ATOMIC) HIPCHK(c, launch_warp_a(a, grid, c->stream));
-        else HIPCHK(c, launch_warp_s(a, run_mode == SMORE_SERIAL ? 1 : grid, c->stream));
+        HIPCHK(c, launch_update(kern, a, grid, c->stream));
         HIPCHK(c, hipEventRecord(c->phase_ev[2 * k + 2], c->stream));
     }
     return finish_timed(c, run_mode, nch);

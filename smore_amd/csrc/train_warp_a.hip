@@ -1,4 +1,4 @@
 // WARP kernel, atomic scatter
 #include "warp_kernels.h"
 
-SMORE_WARP_INST(a, WARP_ATOMIC)
+SMORE_UPDATE_INST(Warp, WARP_ATOMIC, WARP_KMAX, warp_symbol)

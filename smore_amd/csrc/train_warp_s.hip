@@ -1,4 +1,4 @@
 // WARP kernel, plain stores (and the serial mode)
 #include "warp_kernels.h"
 
-SMORE_WARP_INST(s, WARP_STORE)
+SMORE_UPDATE_INST(Warp, WARP_STORE, WARP_KMAX, warp_symbol)

@@ -203,40 +203,17 @@ __global__ void __launch_bounds__(256) warp_train_kernel(WarpArgs a) {
     }
 }
 
-// (G, M) pairs for dpad in [4, 512], as edge_kernels.h SMORE_FOR_EACH_GM
-#define SMORE_WARP_FOR_EACH_GM(X) \
-    X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
-
-template <int MODE>
-struct WarpInst {
-    static hipError_t launch(const WarpArgs& a, int grid, hipStream_t st) {
-        const int G = lanes_of(a.dpad), M = regs_of(a.dpad);
-#define X(g, m)                                                                                   \
-    if (G == g && M == m) {                                                                       \
-        hipLaunchKernelGGL((warp_train_kernel<g, m, MODE>), dim3(grid), dim3(256), 0, st, a);     \
-        return hipGetLastError();                                                                 \
-    }
-        SMORE_WARP_FOR_EACH_GM(X)
-#undef X
-        return hipErrorInvalidValue;
-    }
-    static const void* symbol(int dpad) {
-        const int G = lanes_of(dpad), M = regs_of(dpad);
+// the (G, M) ladder; a unit (train_warp_<s|a>.hip) exports it as its
+// update_symbol specialisation (train_kernels.h SMORE_UPDATE_INST)
+template <int KMAX, int MODE>
+const void* warp_symbol(int dpad, int) {
+    static_assert(KMAX == WARP_KMAX, "one record width");
+    const int G = lanes_of(dpad), M = regs_of(dpad);
 #define X(g, m) \
     if (G == g && M == m) return (const void*)warp_train_kernel<g, m, MODE>;
-        SMORE_WARP_FOR_EACH_GM(X)
+    SMORE_FOR_EACH_GM(X)
 #undef X
-        return nullptr;
-    }
-};
+    return nullptr;
+}
 
 }  // namespace smore
-
-// defines launch_warp_<name>(a, grid, st) and warp_symbol_<name>(dpad)
-#define SMORE_WARP_INST(name, MODE)                                                              \
-    namespace smore {                                                                            \
-    hipError_t launch_warp_##name(const WarpArgs& a, int grid, hipStream_t st) {                 \
-        return WarpInst<MODE>::launch(a, grid, st);                                              \
-    }                                                                                            \
-    const void* warp_symbol_##name(int dpad) { return WarpInst<MODE>::symbol(dpad); }            \
-    }

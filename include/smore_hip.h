@@ -533,6 +533,69 @@ int smore_train_warp_async(smore_ctx* ctx, uint64_t begin, uint64_t count, uint6
  * for the context stream */
 int smore_warp_stats(smore_ctx* ctx, uint64_t* trials, uint64_t* updated);
 
+/* Vertex fields of HOP-REC (replaces: proNet::LoadFieldMeta, src/proNet.cpp:
+ * 330-408; only fields[0], not the per-vertex vids lists).  One int32 per
+ * vertex; field 0 are the users a sample starts from.  Host state: these work
+ * on a host-only context too; the device copy is made by the first training
+ * call.  A new graph drops the fields.
+ *   smore_load_field_meta: "name field" lines, after smore_load_edgelist (the
+ *     names are resolved as smore_load_pretrain does).  A field's id is the
+ *     order of its first appearance in the file, so the first field named is
+ *     field 0; vertices the file does not name keep field 0; names that are
+ *     not in the graph are passed over (their field still takes its id, as in
+ *     the reference).  smore_field_meta_info reports the last load: the
+ *     "name field" lines read and how many of them named no vertex of the
+ *     graph (the reference prints each such name).
+ *   smore_set_fields: field[V] with values in [0, nfields), for graphs from ids.
+ *   smore_get_fields: *nfields (0: none set) and, field non-null, the V values.
+ * Not smore_set_node_types: that builds metapath2vec's typed neighbour index. */
+int smore_load_field_meta(smore_ctx* ctx, const char* path);
+int smore_field_meta_info(const smore_ctx* ctx, int64_t* lines, int64_t* unknown);
+int smore_set_fields(smore_ctx* ctx, const int32_t* field, int nfields);
+int smore_get_fields(const smore_ctx* ctx, int32_t* field, int* nfields);
+
+/* replaces: HBPR::Train (src/model/HBPR.cpp:63-131, the reference's HOP-REC)
+ * over samples [begin, begin + count) of `total` on the ONE table:
+ *   v = SourceSample() until field[v] == 0;  i = TargetSample(v);
+ *   for w = 1 .. walk_steps:  if w > 1: i = TargetSample(TargetSample(i));
+ *     j0 = NegativeSample() until field[j0] == field[i];
+ *     UpdateFBPRPair(v, i, j0, rate alpha / w, margin 1 / w)
+ * UpdateFBPRPair (src/proNet.cpp:1458-1515): five negatives, j1..j4 uniform
+ * indices drawn until they have i's field; per negative x = T[i] - T[j],
+ * f = T[v].x; f > margin does nothing, otherwise g = fastSigmoid(-f) rate,
+ * ve += g x, T[i] and T[j] decay by rate 0.0025 and move by +- g T[v]; after
+ * the five, if `up` of them passed, T[v] decays by rate 0.025 and moves by
+ * ve / up.  Draws: stream 0, unit = sample index, the slots consumed in the
+ * order of the reference's random_gen calls (source attempts 2 slots each,
+ * TargetSample 2, NegativeSample attempts 2 each, in-rule negatives 1 per
+ * attempt): how many a sample uses depends on the fields, not on the tables.
+ * Differences from the reference: a rejection loop gives up after 2^16
+ * attempts and a TargetSample may return -1; the sample stops at that step
+ * (earlier steps stay applied) and counts once in smore_skipped.  Refused
+ * with SMORE_ESTATE without fields, or when no field-0 vertex has source mass
+ * (the reference would loop forever).  walk_steps in 1..10.  alpha: count from
+ * 0 (the BPR law).  Load the graph undirected with negative method
+ * "no_degrees" for the reference's run.  mode: SMORE_SERIAL | SMORE_ATOMIC;
+ * SMORE_HYBRID runs the atomic scatter (smore_last_mode reports
+ * SMORE_ATOMIC); SMORE_HOGWILD is refused with SMORE_EINVAL (whole-row plain
+ * stores lose colliding updates).  One GPU; C++ semantics
+ * only; not while a row census is open. */
+int smore_train_hoprec(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, int walk_steps,
+                       double alpha0, uint64_t seed, int mode);
+int smore_train_hoprec_async(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, int walk_steps,
+                             double alpha0, uint64_t seed, int mode);
+/* margin gates tested (f evaluations) and gates passed (negatives that
+ * updated), summed over every smore_train_hoprec call since
+ * smore_alloc_tables (which zeroes them); waits for the context stream */
+int smore_hoprec_stats(smore_ctx* ctx, uint64_t* tested, uint64_t* passed);
+/* the draws alone: the records of samples [begin, begin + count) --
+ * {v, then per step i_w, j_w0..j_w4}, 1 + 6 walk_steps words padded to a
+ * multiple of 4, vertex ids, -1 from the step where a sample stopped -- into
+ * out, and (slots non-null) the Philox slots each sample consumed.  Changes
+ * neither the tables nor smore_skipped. */
+int smore_hoprec_records(smore_ctx* ctx, uint64_t begin, uint64_t count, int walk_steps, uint64_t seed,
+                         int32_t* out, uint32_t* slots);
+
 /* replaces: proNet::UpdatePairs (src/proNet.cpp:2741-2753) and Go
  * (*ProNet).UpdatePairs (pkg/pronet/optimizer.go:8-18): UpdatePair for each
  * caller-supplied pair (v[i], c[i]), i = 0 .. n-1 in order, with K <= 10

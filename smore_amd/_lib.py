@@ -138,6 +138,14 @@ def _load():
         "smore_train_warp": (i32, [P, u64, u64, u64, dbl, u64, i32]),
         "smore_train_warp_async": (i32, [P, u64, u64, u64, dbl, u64, i32]),
         "smore_warp_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),
+        "smore_load_field_meta": (i32, [P, C.c_char_p]),
+        "smore_field_meta_info": (i32, [P, C.POINTER(i64), C.POINTER(i64)]),
+        "smore_set_fields": (i32, [P, P, i32]),
+        "smore_get_fields": (i32, [P, P, C.POINTER(i32)]),
+        "smore_train_hoprec": (i32, [P, u64, u64, u64, i32, dbl, u64, i32]),
+        "smore_train_hoprec_async": (i32, [P, u64, u64, u64, i32, dbl, u64, i32]),
+        "smore_hoprec_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),
+        "smore_hoprec_records": (i32, [P, u64, u64, i32, u64, P, P]),
         "smore_group_train_walklets": (i32, [P, u64, u64, i32, i32, i32, i32, i32, dbl, u64, i32, u64, i32]),
         "smore_group_train_app": (i32, [P, u64, u64, i32, i32, dbl, i32, dbl, u64, P, i32, u64, i32]),
         "smore_group_train_hpe": (i32, [P, u64, u64, u64, i32, i32, dbl, dbl, u64, i32, u64, i32]),

@@ -62,7 +62,8 @@ void smore_destroy(smore_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
     }
     dfree(c->d_offsets); dfree(c->d_targets); dfree(c->d_vtab); dfree(c->d_ntab); dfree(c->d_ctab);
-    dfree(c->d_sig); dfree(c->d_skipped); dfree(c->d_work); dfree(c->d_warp_stats); dfree(c->d_table[0]); dfree(c->d_table[1]);
+    dfree(c->d_sig); dfree(c->d_skipped); dfree(c->d_work); dfree(c->d_warp_stats); dfree(c->d_field); dfree(c->d_hoprec_slots); dfree(c->d_hoprec_stats);
+    dfree(c->d_table[0]); dfree(c->d_table[1]);
 
     dfree(c->d_order); dfree(c->d_walks); dfree(c->d_lens); dfree(c->d_tcum); dfree(c->d_wts); dfree(c->d_nbr_sorted); dfree(c->d_ntype); dfree(c->d_ttargets); dfree(c->d_toff); dfree(c->d_paths); dfree(c->d_path_off); dfree(c->d_t_off); dfree(c->d_t_tgt); dfree(c->d_t_ts); dfree(c->d_t_min); dfree(c->d_t_max); dfree(c->d_sh_hash); dfree(c->d_sh_ids);
     dfree(c->d_rec); dfree(c->d_vt32); dfree(c->d_ct16); dfree(c->d_split);
@@ -219,6 +220,7 @@ int smore_set_alias(smore_ctx* c, int which, const double* prob, const int64_t* 
     P.assign(prob, prob + n);
     A.assign(alias, alias + n);
     c->hot_key.clear();
+    if (which == 0) c->field_src = -1;   // a new source law
     T.resize((size_t)n);
     alias_encode(P.data(), A.data(), n, which == SMORE_AT_CONTEXT ? g.targets.data() : nullptr, T.data());
     if (c->device < 0) return SMORE_OK;
@@ -291,6 +293,7 @@ int smore_alloc_tables(smore_ctx* c, int dim, int ntables) {
     for (int t = 0; t < ntables; ++t) HIPCHK(c, hipMemset(c->d_table[t], 0, t == 1 ? cbytes : bytes));
     c->blk.key.clear();   // the block tables' hub slots live in the new C table
     if (c->d_warp_stats) HIPCHK(c, hipMemset(c->d_warp_stats, 0, 2 * sizeof(unsigned long long)));
+    if (c->d_hoprec_stats) HIPCHK(c, hipMemset(c->d_hoprec_stats, 0, 2 * sizeof(unsigned long long)));
     return SMORE_OK;
 }
 
@@ -362,6 +365,7 @@ int smore_set_semantics(smore_ctx* c, int semantics) {
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (semantics == c->semantics) return SMORE_OK;
     c->packed_ok = false;
+    c->field_src = -1;   // a new source law
     std::vector<double> tcum;
     if (semantics == SMORE_SEM_GO) build_go_tables(*c->g, tcum);
     else build_cpp_vn_tables(*c->g);

@@ -42,6 +42,17 @@ struct smore_ctx {
     unsigned long long* d_work = nullptr;   // chunk counter of the Hogwild edge kernels
     unsigned long long* d_warp_stats = nullptr;   // WARP: {trials executed, samples that updated} (smore_warp_stats)
     double warp_rows = 0.0;             // WARP: effective rows of the plain-store cap (train_warp.cpp; 0: not computed)
+    // HOP-REC (train_hoprec.cpp): vertex fields (smore_set_fields / smore_load_field_meta), V entries once
+    // set; the device copy is uploaded by the first training call; {gates tested, gates passed}
+    std::vector<int32_t> field;
+    int nfields = 0;
+    int field_src = -1;                 // a field-0 vertex has source mass: -1 not looked at (new fields or a new
+                                        // source law: smore_set_alias, smore_set_semantics), 0 no, 1 yes
+    int64_t field_lines = 0, field_unknown = 0;   // smore_load_field_meta: lines read, names not in the graph
+    int32_t* d_field = nullptr;
+    uint32_t* d_hoprec_slots = nullptr; // smore_hoprec_records: slots per sample
+    size_t hoprec_slots_cap = 0;
+    unsigned long long* d_hoprec_stats = nullptr;
     // tables
     float* d_table[2] = {nullptr, nullptr};
     int dim = 0, dpad = 0, ntables = 0;
@@ -330,6 +341,10 @@ inline int upload_graph(smore_ctx* c) {
     c->census_rate[0].clear();
     c->census_rate[1].clear();
     c->warp_rows = 0.0;
+    c->field.clear();                   // the fields belong to the previous graph's vertices
+    c->nfields = 0;
+    c->field_src = -1;
+    dfree(c->d_field);
     dfree(c->d_census[0]);
     dfree(c->d_census[1]);
     blocks_release(c);

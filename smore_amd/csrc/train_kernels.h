@@ -224,10 +224,37 @@ struct WarpArgs {
     int groups;                    // sample groups of a block that take samples (<= 256 / G; the rest idle)
 };
 
+// HOP-REC (hoprec_kernels.h; train_hoprec_<s|a>.hip): a sample is walk_steps
+// ranking steps on {v, i_w, j_w0..j_w4}, every id pre-drawn by
+// hoprec_draw_kernel (train_hoprec_draw.hip) from the sample's Philox unit
+constexpr int HOPREC_NEG = 5;                // negatives per step (src/proNet.cpp:1472)
+constexpr int HOPREC_MAX_STEPS = 10;         // walk_steps accepted
+constexpr int HOPREC_KMAX = 5;               // the family's one instantiation bucket
+constexpr uint32_t HOPREC_ATTEMPTS = 1u << 16;   // a rejection loop gives up after this many draws
+// int32 words of a record {v, then per step i_w, j_w0..j_w4}: padded to whole 16-B words
+constexpr int hoprec_width(int steps) { return (1 + (1 + HOPREC_NEG) * steps + 3) & ~3; }
+
+struct HopRecArgs {
+    const float* sig;              // 1001-entry fastSigmoid table
+    float* T;                      // [V][dpad], the one table
+    const int32_t* rec;            // hoprec_width(steps) words per sample (tagged ids; -1 from the step a sample stopped at)
+    unsigned long long* work;      // chunk counter, zeroed per launch
+    unsigned long long* stats;     // {gates tested, gates passed}, accumulated
+    uint64_t begin, count, total;
+    double alpha0;
+    int dpad, mode;                // mode: SMORE_* scatter (2 = serial)
+    int steps;                     // walk_steps
+};
+// the draws of samples [begin, begin + count): records, and (slots non-null) the
+// Philox slots each sample consumed; a sample that stopped early is counted in *skipped
+hipError_t launch_hoprec_draw(const DevGraph& g, const int32_t* field, uint64_t seed, uint64_t begin, uint64_t count,
+                              int steps, int32_t* rec, uint32_t* slots, unsigned long long* skipped, hipStream_t st);
+
 // ---------------------------------------------------------------- update kernels
 // The kernels that turn records into row updates: edge_train_kernel and
 // pair_train_kernel (edge_kernels.h), go_rec_kernel and go_pair_kernel
-// (go_rec.h), warp_train_kernel (warp_kernels.h).  Each takes its argument
+// (go_rec.h), warp_train_kernel (warp_kernels.h), hoprec_train_kernel
+// (hoprec_kernels.h).  Each takes its argument
 // struct as its one by-value parameter and exists per scatter MODE, KMAX
 // bucket and (G, M) lane layout.
 
@@ -237,11 +264,12 @@ struct WarpArgs {
 #define SMORE_FOR_EACH_GM(X) \
     X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
 
-enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp };
+enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec };
 
 // Every (family, MODE, KMAX) instantiation.  Each is built in a unit of its
 // own (train_edge_<mode>_k<KMAX>.hip, train_pair_<s|a|h><KMAX>.hip,
-// train_warp_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a mode's four Go ones),
+// train_warp_<s|a>.hip, train_hoprec_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a
+// mode's four Go ones),
 // so a new bucket is one line here and its .hip file.
 #define SMORE_FOR_EACH_UPDATE_KERNEL(X)                                             \
     X(Edge, MODE_STORE, 5) X(Edge, MODE_STORE, 10) X(Edge, MODE_STORE, 20)          \
@@ -256,7 +284,8 @@ enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp };
     X(GoPair, MODE_STORE, 5) X(GoPair, MODE_STORE, 10)                              \
     X(GoPair, MODE_ATOMIC, 5) X(GoPair, MODE_ATOMIC, 10)                            \
     X(GoPair, MODE_HYBRID, 5) X(GoPair, MODE_HYBRID, 10)                            \
-    X(Warp, WARP_STORE, WARP_KMAX) X(Warp, WARP_ATOMIC, WARP_KMAX)
+    X(Warp, WARP_STORE, WARP_KMAX) X(Warp, WARP_ATOMIC, WARP_KMAX)                  \
+    X(HopRec, MODE_STORE, HOPREC_KMAX) X(HopRec, MODE_ATOMIC, HOPREC_KMAX)
 
 // The instantiation's kernel for dpad's lane layout (Edge: and the model's
 // rule), or nullptr when there is none: a (G, M) outside the list, BPR with
@@ -291,6 +320,7 @@ struct UpdateKernel {
 };
 UpdateKernel update_kernel(UpdateFamily f, const EdgeArgs& a);
 UpdateKernel update_kernel(const WarpArgs& a);
+UpdateKernel update_kernel(const HopRecArgs& a);
 
 // the one launch of the update kernels: 256 threads, `a` as the kernel's parameter
 template <class Args>

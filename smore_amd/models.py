@@ -1,5 +1,5 @@
 """Model drivers mirroring the reference's C++ model classes
-(src/model/{LINE,MF,BPR,WARP,DeepWalk,Walklets,APP,HPE}.h): LoadEdgeList / Init / Train / SaveWeights
+(src/model/{LINE,MF,BPR,WARP,HBPR,DeepWalk,Walklets,APP,HPE}.h): LoadEdgeList / Init / Train / SaveWeights
 with the same argument meaning, banners and learning-rate schedule.  The hot
 loop is one HIP launch per chunk through the C ABI.
 
@@ -167,6 +167,41 @@ class WARP(_EdgeModel):
         while done < total:
             n = min(CHUNK, total - done)
             self.pnet.train_warp(done, n, total, alpha, self.seed, self.mode)
+            done += n
+            _progress(_alpha_at(done, alpha, total), done / total)
+        _progress(_alpha_at(total, alpha, total), 1.0, "\n")
+
+
+class HBPR(_EdgeModel):
+    """HOP-REC (src/model/HBPR.{h,cpp}): per sample a field-0 source, then walk_steps
+    UpdateFBPRPair steps at rate alpha / w and margin 1 / w on positives further along
+    a random walk, five same-field negatives each.  "hybrid" runs the atomic scatter;
+    there is no plain-store ("hogwild") scatter."""
+
+    def __init__(self, device=0, mode="hybrid", seed=1):
+        super().__init__(device, mode, seed)
+        self.pnet.SetNegativeMethod("no_degrees")   # src/model/HBPR.cpp:4-7
+
+    def LoadFieldMeta(self, filename):
+        self.pnet.LoadFieldMeta(filename)
+
+    def Init(self, dim):
+        print("Model Setting:\n\tdimension:\t\t%d" % dim)
+        self.dim = dim
+        self.pnet.alloc_tables(dim, 1)
+        self.pnet.init_table_glibc(_lib.W, 0)       # src/model/HBPR.cpp:50-54 (w_context is never trained)
+
+    def Train(self, sample_times, walk_steps, alpha, workers=1, samples=None):
+        # samples (an extension, like seed): the exact number of samples instead of sample_times * 10^6
+        print("Model:\n\t[HBPR]\nLearning Parameters:")
+        print("\tsample_times:\t\t%d\n\talpha:\t\t\t%g\n\twalk steps:\t\t%d\n\tworkers:\t\t%d"
+              % (sample_times, alpha, walk_steps, workers))
+        print("Start Training:")
+        total = int(sample_times) * 1000000 if samples is None else int(samples)
+        done = 0
+        while done < total:
+            n = min(CHUNK, total - done)
+            self.pnet.train_hoprec(done, n, total, walk_steps, alpha, self.seed, self.mode)
             done += n
             _progress(_alpha_at(done, alpha, total), done / total)
         _progress(_alpha_at(total, alpha, total), 1.0, "\n")

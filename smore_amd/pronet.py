@@ -491,6 +491,56 @@ class ProNet:
         self._chk(lib.smore_warp_stats(self.ctx, C.byref(t), C.byref(u)), "warp_stats")
         return t.value, u.value
 
+    # ---------------------------------------------------------------- HOP-REC
+    def LoadFieldMeta(self, filename):
+        """proNet::LoadFieldMeta (src/proNet.cpp:330-408): "name field" lines; the first
+        field named in the file is field 0 (the users).  Returns (lines read, names that
+        are not in the graph and were passed over)."""
+        self._chk(lib.smore_load_field_meta(self.ctx, filename.encode()), "LoadFieldMeta(%s)" % filename)
+        n, u = C.c_int64(), C.c_int64()
+        self._chk(lib.smore_field_meta_info(self.ctx, C.byref(n), C.byref(u)), "field_meta_info")
+        return n.value, u.value
+
+    def set_fields(self, field, nfields):
+        """Vertex fields from ids: field[V] in [0, nfields)."""
+        field = np.ascontiguousarray(field, np.int32)
+        if field.shape != (self.MAX_vid,):
+            raise ValueError("set_fields: one field per vertex")
+        self._chk(lib.smore_set_fields(self.ctx, ptr(field), int(nfields)), "set_fields")
+
+    @property
+    def fields(self):
+        """(field[V] int32, number of fields), or (None, 0) when none are set."""
+        n = C.c_int()
+        self._chk(lib.smore_get_fields(self.ctx, None, C.byref(n)), "get_fields")
+        if n.value == 0:
+            return None, 0
+        f = np.zeros(self.MAX_vid, np.int32)
+        self._chk(lib.smore_get_fields(self.ctx, ptr(f), C.byref(n)), "get_fields")
+        return f, n.value
+
+    def train_hoprec(self, begin, count, total, walk_steps, alpha0, seed=1, mode="atomic", sync=True):
+        """HBPR::Train (src/model/HBPR.cpp:63-131) over samples [begin, begin + count) of total."""
+        fn = lib.smore_train_hoprec if sync else lib.smore_train_hoprec_async
+        self._chk(fn(self.ctx, int(begin), int(count), int(total), int(walk_steps), float(alpha0), int(seed),
+                     _lib.MODE[mode]), "train_hoprec")
+
+    def hoprec_stats(self):
+        """(margin gates tested, gates passed) of the HOP-REC calls since alloc_tables."""
+        t, u = C.c_uint64(), C.c_uint64()
+        self._chk(lib.smore_hoprec_stats(self.ctx, C.byref(t), C.byref(u)), "hoprec_stats")
+        return t.value, u.value
+
+    def hoprec_records(self, begin, count, walk_steps, seed):
+        """The draws of samples [begin, begin + count): (records [count][1 + 6 walk_steps
+        padded to 4] of vertex ids, -1 from the step a sample stopped at; slots consumed)."""
+        rw = (1 + 6 * int(walk_steps) + 3) // 4 * 4
+        out = np.zeros((int(count), rw), np.int32)
+        slots = np.zeros(int(count), np.uint32)
+        self._chk(lib.smore_hoprec_records(self.ctx, int(begin), int(count), int(walk_steps), int(seed), ptr(out),
+                                           ptr(slots)), "hoprec_records")
+        return out, slots
+
     def set_semantics(self, semantics):
         """"cpp" (src/proNet.cpp rules, default) or "go" (pkg/pronet rules)."""
         self._chk(lib.smore_set_semantics(self.ctx, _lib.SEM[semantics]), "set_semantics")

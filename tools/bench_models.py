@@ -17,6 +17,10 @@ calls after one warmup call, inputs resident in HBM.
   c5go / c5n2v  Go DeepWalk / Go node2vec (p 0.5, q 2) on c5's graph
   warp WARP on c3's graph, d=128 (M WARP samples/s, and the mean trials per
        sample from smore_warp_stats; "hybrid" runs the atomic scatter)
+  hoprec HOP-REC on c3's graph loaded undirected, d=128, walk_steps 5, fields
+       from the generator's user / item split (M HOP-REC samples/s, the gates
+       passed per sample from smore_hoprec_stats, draw / update ms; "hybrid"
+       runs the atomic scatter, there is no plain-store one)
 """
 import argparse
 import json
@@ -69,11 +73,16 @@ def main():
     import smore_amd
     from smore_amd import graphgen
     for cfg in args.configs:
-        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg == "warp" else cfg)
+        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec") else cfg)
         pn = smore_amd.ProNet(0)
         t0 = time.perf_counter()
-        if cfg in ("c3", "warp"):
-            pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
+        if cfg in ("c3", "warp", "hoprec"):
+            pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() / HBPR() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
+        if cfg == "hoprec":
+            # HBPR loads undirected (cli/hoprec.cpp:63): every line also as item -> user
+            users = int(src.max()) + 1               # the generator's split: users [0, users), items after them
+            assert int(dst.min()) >= users
+            src, dst, w = np.concatenate([src, dst]), np.concatenate([dst, src]), np.concatenate([w, w])
         pn.set_graph_edges(V, src, dst, w)
         build = time.perf_counter() - t0
         out = {"config": cfg, "vertices": V, "edge_slots": pn.MAX_line, "mode": args.mode,
@@ -112,6 +121,25 @@ def main():
                        trials_per_sample=round((st[-1][0] - st[0][0]) / (args.steps * S), 4),
                        updated_per_sample=round((st[-1][1] - st[0][1]) / (args.steps * S), 4),
                        value=round(S / ms / 1e3, 1), unit="M WARP samples/s")
+        elif cfg == "hoprec":
+            S, walk_steps = 1 << 24, 5
+            pn.set_fields((np.arange(V) >= users).astype(np.int32), 2)
+            pn.alloc_tables(128, 1)
+            pn.init_table_uniform(0, 1)
+            total = (args.steps + 1) * S
+            ms, ph, st = [], [], []
+            for k in range(args.steps + 1):
+                pn.train_hoprec(k * S, S, total, walk_steps, 0.025, 7, args.mode)
+                st.append(pn.hoprec_stats())
+                if k:
+                    ms.append(pn.last_kernel_ms())
+                    ph.append(pn.last_phase_ms()[:2])
+            ms = float(np.mean(ms))
+            out.update(model="hoprec", dim=128, walk_steps=walk_steps, samples_per_call=S, ms_per_call=round(ms, 3),
+                       draw_update_ms=[round(float(x), 3) for x in np.mean(ph, axis=0)],
+                       gates_passed_per_sample=round((st[-1][1] - st[0][1]) / (args.steps * S), 4),
+                       skipped=pn.skipped(),
+                       value=round(S / ms / 1e3, 2), unit="M HOP-REC samples/s")
         elif cfg == "c5":
             steps_, window, K, walk_times = 40, 5, 5, 1
             pn.alloc_tables(128, 2)

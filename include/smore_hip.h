@@ -133,6 +133,10 @@ int smore_alloc_tables(smore_ctx* ctx, int dim, int ntables);
  * table[v][d] = (rand()/RAND_MAX - 0.5)/dim with glibc rand() seeded by srand(1),
  * skipping the first `skip` draws (so W then C reproduce the reference order). */
 int smore_init_table_glibc(smore_ctx* ctx, int which, uint64_t skip);
+/* replaces: SPR::Init (src/model/SkewOPT.cpp:45-50): the same draws,
+ * table[v][d] = (rand()/RAND_MAX - 0.5)/dim + offset evaluated in double and
+ * rounded to float once */
+int smore_init_table_glibc_offset(smore_ctx* ctx, int which, uint64_t skip, double offset);
 /* on-device init (Philox stream 2): (u - 0.5)/dim, u uniform in [0,1) */
 int smore_init_table_uniform(smore_ctx* ctx, int which, uint64_t seed);
 int smore_zero_table(smore_ctx* ctx, int which);
@@ -532,6 +536,34 @@ int smore_train_warp_async(smore_ctx* ctx, uint64_t begin, uint64_t count, uint6
  * smore_train_warp call since smore_alloc_tables (which zeroes them); waits
  * for the context stream */
 int smore_warp_stats(smore_ctx* ctx, uint64_t* trials, uint64_t* updated);
+
+/* replaces: SPR::Train (src/model/SkewOPT.cpp:55-110, Skew-OPT) over samples
+ * [begin, begin + count) of `total` on the ONE table: v = SourceSample,
+ * i = TargetSample(v), then UpdateSBPRPair (src/proNet.cpp:1517-1566): sixteen
+ * negatives j = NegativeSample(), each on the current rows: x = T[i] - T[j],
+ * f = T[v].x, g = (f - xi) / omega; g > 2 skips the negative, g < -2 is
+ * clamped to -2; p = g^eta, gg = fastSigmoid(-p) (p / g) / omega alpha;
+ * T[i], T[j] decay by alpha * 0.01 and move by +- gg T[v]; after the sixteen,
+ * if `up` > 0 passed, T[v] decays and moves by (sum gg x) / up.  The
+ * reference's reg argument is never used and has no counterpart here.  At
+ * g == 0 (f == xi exactly) the reference divides 0 by 0; here p / g is its
+ * limit, 0 for eta >= 2 and 1 for eta == 1.  Draws: stream 0, unit = sample
+ * index, slots 0-3 source and target, slots 4 + 2n, 5 + 2n negative n (the
+ * 4 + 2K layout, K = 16).  A source without out-edge is counted in
+ * smore_skipped.  alpha: count from 0 (the BPR law).  Needs the negative
+ * method the caller wants (the reference sets "no_degrees").
+ * mode: SMORE_SERIAL | SMORE_ATOMIC; SMORE_HYBRID runs the atomic scatter
+ * (smore_last_mode reports SMORE_ATOMIC); SMORE_HOGWILD is refused
+ * (SMORE_EINVAL), as are omega == 0 and eta < 1.  One GPU; C++ semantics
+ * only; not while a row census is open. */
+int smore_train_skewopt(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, double alpha0,
+                        double xi, double omega, int eta, uint64_t seed, int mode);
+int smore_train_skewopt_async(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, double alpha0,
+                              double xi, double omega, int eta, uint64_t seed, int mode);
+/* negatives that passed the gate and samples that updated, summed over every
+ * smore_train_skewopt call since smore_alloc_tables (which zeroes them);
+ * waits for the context stream */
+int smore_skewopt_stats(smore_ctx* ctx, uint64_t* passed, uint64_t* updated);
 
 /* Vertex fields of HOP-REC (replaces: proNet::LoadFieldMeta, src/proNet.cpp:
  * 330-408; only fields[0], not the per-vertex vids lists).  One int32 per

@@ -62,6 +62,7 @@ def _load():
         "smore_get_alias_encoded": (i32, [P, i32, P, P, i64]),
         "smore_alloc_tables": (i32, [P, i32, i32]),
         "smore_init_table_glibc": (i32, [P, i32, u64]),
+        "smore_init_table_glibc_offset": (i32, [P, i32, u64, dbl]),
         "smore_init_table_uniform": (i32, [P, i32, u64]),
         "smore_zero_table": (i32, [P, i32]),
         "smore_set_table": (i32, [P, i32, P, i64, i32]),
@@ -142,6 +143,9 @@ def _load():
         "smore_field_meta_info": (i32, [P, C.POINTER(i64), C.POINTER(i64)]),
         "smore_set_fields": (i32, [P, P, i32]),
         "smore_get_fields": (i32, [P, P, C.POINTER(i32)]),
+        "smore_train_skewopt": (i32, [P, u64, u64, u64, dbl, dbl, dbl, i32, u64, i32]),
+        "smore_train_skewopt_async": (i32, [P, u64, u64, u64, dbl, dbl, dbl, i32, u64, i32]),
+        "smore_skewopt_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),
         "smore_train_hoprec": (i32, [P, u64, u64, u64, i32, dbl, u64, i32]),
         "smore_train_hoprec_async": (i32, [P, u64, u64, u64, i32, dbl, u64, i32]),
         "smore_hoprec_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),

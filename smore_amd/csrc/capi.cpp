@@ -62,7 +62,7 @@ void smore_destroy(smore_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
     }
     dfree(c->d_offsets); dfree(c->d_targets); dfree(c->d_vtab); dfree(c->d_ntab); dfree(c->d_ctab);
-    dfree(c->d_sig); dfree(c->d_skipped); dfree(c->d_work); dfree(c->d_warp_stats); dfree(c->d_field); dfree(c->d_hoprec_slots); dfree(c->d_hoprec_stats);
+    dfree(c->d_sig); dfree(c->d_skipped); dfree(c->d_work); dfree(c->d_warp_stats); dfree(c->d_field); dfree(c->d_hoprec_slots); dfree(c->d_hoprec_stats); dfree(c->d_skewopt_stats);
     dfree(c->d_table[0]); dfree(c->d_table[1]);
 
     dfree(c->d_order); dfree(c->d_walks); dfree(c->d_lens); dfree(c->d_tcum); dfree(c->d_wts); dfree(c->d_nbr_sorted); dfree(c->d_ntype); dfree(c->d_ttargets); dfree(c->d_toff); dfree(c->d_paths); dfree(c->d_path_off); dfree(c->d_t_off); dfree(c->d_t_tgt); dfree(c->d_t_ts); dfree(c->d_t_min); dfree(c->d_t_max); dfree(c->d_sh_hash); dfree(c->d_sh_ids);
@@ -294,6 +294,7 @@ int smore_alloc_tables(smore_ctx* c, int dim, int ntables) {
     c->blk.key.clear();   // the block tables' hub slots live in the new C table
     if (c->d_warp_stats) HIPCHK(c, hipMemset(c->d_warp_stats, 0, 2 * sizeof(unsigned long long)));
     if (c->d_hoprec_stats) HIPCHK(c, hipMemset(c->d_hoprec_stats, 0, 2 * sizeof(unsigned long long)));
+    if (c->d_skewopt_stats) HIPCHK(c, hipMemset(c->d_skewopt_stats, 0, 2 * sizeof(unsigned long long)));
     return SMORE_OK;
 }
 
@@ -306,6 +307,20 @@ int smore_init_table_glibc(smore_ctx* c, int which, uint64_t skip) {
     for (int64_t v = 0; v < c->g->V; ++v)
         for (int d = 0; d < c->dim; ++d)
             h[(size_t)v * c->dpad + d] = (float)((r.next() / (double)2147483647 - 0.5) / c->dim);
+    if ((rc = set_device(c))) return rc;
+    HIPCHK(c, hipMemcpy(c->d_table[which], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return SMORE_OK;
+}
+
+int smore_init_table_glibc_offset(smore_ctx* c, int which, uint64_t skip, double offset) {
+    int rc;
+    if ((rc = check_table(c, which))) return rc;
+    GlibcRand r;
+    r.discard(skip);
+    std::vector<float> h((size_t)c->g->V * c->dpad, 0.0f);
+    for (int64_t v = 0; v < c->g->V; ++v)
+        for (int d = 0; d < c->dim; ++d)
+            h[(size_t)v * c->dpad + d] = (float)((r.next() / (double)2147483647 - 0.5) / c->dim + offset);
     if ((rc = set_device(c))) return rc;
     HIPCHK(c, hipMemcpy(c->d_table[which], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     return SMORE_OK;

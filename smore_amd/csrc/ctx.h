@@ -53,6 +53,7 @@ struct smore_ctx {
     uint32_t* d_hoprec_slots = nullptr; // smore_hoprec_records: slots per sample
     size_t hoprec_slots_cap = 0;
     unsigned long long* d_hoprec_stats = nullptr;
+    unsigned long long* d_skewopt_stats = nullptr;   // Skew-OPT: {gates passed, samples that updated} (smore_skewopt_stats)
     // tables
     float* d_table[2] = {nullptr, nullptr};
     int dim = 0, dpad = 0, ntables = 0;

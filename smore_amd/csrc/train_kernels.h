@@ -250,11 +250,29 @@ struct HopRecArgs {
 hipError_t launch_hoprec_draw(const DevGraph& g, const int32_t* field, uint64_t seed, uint64_t begin, uint64_t count,
                               int steps, int32_t* rec, uint32_t* slots, unsigned long long* skipped, hipStream_t st);
 
+// Skew-OPT (skewopt_kernels.h; train_skewopt_<s|a>.hip): one positive pair and
+// sixteen negatives per sample, every id pre-drawn by launch_draw with K = 16
+constexpr int SKEW_NEG = 16;                 // negatives per sample (src/proNet.cpp:1532)
+constexpr int SKEWOPT_KMAX = 20;             // record width of the K = 16 draw: rec_width(20) = 32 words
+
+struct SkewOptArgs {
+    const float* sig;              // 1001-entry fastSigmoid table
+    float* T;                      // [V][dpad], the one table
+    const int32_t* rec;            // {v, i, j_0..j_15, -1 ..} per sample, rec_width(SKEWOPT_KMAX) words (tagged ids)
+    unsigned long long* work;      // chunk counter, zeroed per launch
+    unsigned long long* stats;     // {gates passed, samples that updated}, accumulated
+    uint64_t begin, count, total;
+    double alpha0;
+    float xi, omega;               // the rule's margin and scale, rounded to fp32 once
+    int eta;                       // the power (>= 1)
+    int dpad, mode;                // mode: SMORE_* scatter (2 = serial)
+};
+
 // ---------------------------------------------------------------- update kernels
 // The kernels that turn records into row updates: edge_train_kernel and
 // pair_train_kernel (edge_kernels.h), go_rec_kernel and go_pair_kernel
 // (go_rec.h), warp_train_kernel (warp_kernels.h), hoprec_train_kernel
-// (hoprec_kernels.h).  Each takes its argument
+// (hoprec_kernels.h), skewopt_train_kernel (skewopt_kernels.h).  Each takes its argument
 // struct as its one by-value parameter and exists per scatter MODE, KMAX
 // bucket and (G, M) lane layout.
 
@@ -264,11 +282,11 @@ hipError_t launch_hoprec_draw(const DevGraph& g, const int32_t* field, uint64_t 
 #define SMORE_FOR_EACH_GM(X) \
     X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
 
-enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec };
+enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt };
 
 // Every (family, MODE, KMAX) instantiation.  Each is built in a unit of its
 // own (train_edge_<mode>_k<KMAX>.hip, train_pair_<s|a|h><KMAX>.hip,
-// train_warp_<s|a>.hip, train_hoprec_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a
+// train_warp_<s|a>.hip, train_hoprec_<s|a>.hip, train_skewopt_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a
 // mode's four Go ones),
 // so a new bucket is one line here and its .hip file.
 #define SMORE_FOR_EACH_UPDATE_KERNEL(X)                                             \
@@ -285,7 +303,8 @@ enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec };
     X(GoPair, MODE_ATOMIC, 5) X(GoPair, MODE_ATOMIC, 10)                            \
     X(GoPair, MODE_HYBRID, 5) X(GoPair, MODE_HYBRID, 10)                            \
     X(Warp, WARP_STORE, WARP_KMAX) X(Warp, WARP_ATOMIC, WARP_KMAX)                  \
-    X(HopRec, MODE_STORE, HOPREC_KMAX) X(HopRec, MODE_ATOMIC, HOPREC_KMAX)
+    X(HopRec, MODE_STORE, HOPREC_KMAX) X(HopRec, MODE_ATOMIC, HOPREC_KMAX)          \
+    X(SkewOpt, MODE_STORE, SKEWOPT_KMAX) X(SkewOpt, MODE_ATOMIC, SKEWOPT_KMAX)
 
 // The instantiation's kernel for dpad's lane layout (Edge: and the model's
 // rule), or nullptr when there is none: a (G, M) outside the list, BPR with
@@ -321,6 +340,7 @@ struct UpdateKernel {
 UpdateKernel update_kernel(UpdateFamily f, const EdgeArgs& a);
 UpdateKernel update_kernel(const WarpArgs& a);
 UpdateKernel update_kernel(const HopRecArgs& a);
+UpdateKernel update_kernel(const SkewOptArgs& a);
 
 // the one launch of the update kernels: 256 threads, `a` as the kernel's parameter
 template <class Args>

@@ -1,5 +1,5 @@
 """Model drivers mirroring the reference's C++ model classes
-(src/model/{LINE,MF,BPR,WARP,HBPR,DeepWalk,Walklets,APP,HPE}.h): LoadEdgeList / Init / Train / SaveWeights
+(src/model/{LINE,MF,BPR,WARP,HBPR,SkewOPT,DeepWalk,Walklets,APP,HPE}.h): LoadEdgeList / Init / Train / SaveWeights
 with the same argument meaning, banners and learning-rate schedule.  The hot
 loop is one HIP launch per chunk through the C ABI.
 
@@ -167,6 +167,39 @@ class WARP(_EdgeModel):
         while done < total:
             n = min(CHUNK, total - done)
             self.pnet.train_warp(done, n, total, alpha, self.seed, self.mode)
+            done += n
+            _progress(_alpha_at(done, alpha, total), done / total)
+        _progress(_alpha_at(total, alpha, total), 1.0, "\n")
+
+
+class SPR(_EdgeModel):
+    """Skew-OPT (src/model/SkewOPT.{h,cpp}): UpdateSBPRPair on one table -- per
+    sample one positive pair and sixteen uniform negatives through the skewed
+    gate g = (f - xi) / omega, power eta.  "hybrid" runs the atomic scatter;
+    there is no plain-store ("hogwild") scatter."""
+
+    def __init__(self, device=0, mode="hybrid", seed=1):
+        super().__init__(device, mode, seed)
+        self.pnet.SetNegativeMethod("no_degrees")   # src/model/SkewOPT.cpp:4-7
+
+    def Init(self, dim):
+        print("Model Setting:\n\tdimension:\t\t%d" % dim)
+        self.dim = dim
+        self.pnet.alloc_tables(dim, 1)
+        self.pnet.init_table_glibc_offset(_lib.W, 0, 0.01)   # src/model/SkewOPT.cpp:45-50
+
+    def Train(self, sample_times, negative_samples, alpha, reg, xi, omega, eta, workers=1):
+        # `negative_samples` and `reg` are ignored by the reference rule
+        # (src/proNet.cpp:1517-1566: sixteen negatives, decay 0.01); reg is printed
+        print("Model:\n\t[Skew-OPT]\nLearning Parameters:")
+        print("\tsample_times:\t\t%d\n\talpha:\t\t\t%g\n\tregularization:\t\t%g\n\txi:\t\t\t%g\n"
+              "\tomega:\t\t\t%g\n\teta:\t\t\t%d\n\tworkers:\t\t%d" % (sample_times, alpha, reg, xi, omega, eta, workers))
+        print("Start Training:")
+        total = int(sample_times) * 1000000
+        done = 0
+        while done < total:
+            n = min(CHUNK, total - done)
+            self.pnet.train_skewopt(done, n, total, alpha, xi, omega, eta, self.seed, self.mode)
             done += n
             _progress(_alpha_at(done, alpha, total), done / total)
         _progress(_alpha_at(total, alpha, total), 1.0, "\n")

@@ -155,6 +155,10 @@ class ProNet:
         self._chk(lib.smore_alloc_tables(self.ctx, int(dim), int(ntables)), "alloc_tables")
         self.dim = dim
 
+    def init_table_glibc_offset(self, which, skip=0, offset=0.0):
+        self._chk(lib.smore_init_table_glibc_offset(self.ctx, which, int(skip), float(offset)),
+                  "init_table_glibc_offset")
+
     def init_table_glibc(self, which, skip=0):
         self._chk(lib.smore_init_table_glibc(self.ctx, which, int(skip)), "init_table_glibc")
 
@@ -518,6 +522,18 @@ class ProNet:
         f = np.zeros(self.MAX_vid, np.int32)
         self._chk(lib.smore_get_fields(self.ctx, ptr(f), C.byref(n)), "get_fields")
         return f, n.value
+
+    def train_skewopt(self, begin, count, total, alpha0, xi=10.0, omega=3.0, eta=3, seed=1, mode="atomic", sync=True):
+        """SPR::Train (src/model/SkewOPT.cpp:55-110) over samples [begin, begin + count) of total."""
+        fn = lib.smore_train_skewopt if sync else lib.smore_train_skewopt_async
+        self._chk(fn(self.ctx, int(begin), int(count), int(total), float(alpha0), float(xi), float(omega), int(eta),
+                     int(seed), _lib.MODE[mode]), "train_skewopt")
+
+    def skewopt_stats(self):
+        """(negatives that passed the gate, samples that updated) of the Skew-OPT calls since alloc_tables."""
+        p, u = C.c_uint64(), C.c_uint64()
+        self._chk(lib.smore_skewopt_stats(self.ctx, C.byref(p), C.byref(u)), "skewopt_stats")
+        return p.value, u.value
 
     def train_hoprec(self, begin, count, total, walk_steps, alpha0, seed=1, mode="atomic", sync=True):
         """HBPR::Train (src/model/HBPR.cpp:63-131) over samples [begin, begin + count) of total."""

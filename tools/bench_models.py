@@ -21,6 +21,10 @@ calls after one warmup call, inputs resident in HBM.
        from the generator's user / item split (M HOP-REC samples/s, the gates
        passed per sample from smore_hoprec_stats, draw / update ms; "hybrid"
        runs the atomic scatter, there is no plain-store one)
+  skewopt Skew-OPT on c3's graph, d=128, defaults xi 10 / omega 3 / eta 3 from
+       SPR::Init's table (M Skew-OPT samples/s and M rows/s: 18 rows read per
+       sample plus the rows written, from smore_skewopt_stats; "hybrid" runs
+       the atomic scatter, there is no plain-store one)
 """
 import argparse
 import json
@@ -73,11 +77,11 @@ def main():
     import smore_amd
     from smore_amd import graphgen
     for cfg in args.configs:
-        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec") else cfg)
+        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt") else cfg)
         pn = smore_amd.ProNet(0)
         t0 = time.perf_counter()
-        if cfg in ("c3", "warp", "hoprec"):
-            pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() / HBPR() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
+        if cfg in ("c3", "warp", "hoprec", "skewopt"):
+            pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() / HBPR() / SPR() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
         if cfg == "hoprec":
             # HBPR loads undirected (cli/hoprec.cpp:63): every line also as item -> user
             users = int(src.max()) + 1               # the generator's split: users [0, users), items after them
@@ -140,6 +144,27 @@ def main():
                        gates_passed_per_sample=round((st[-1][1] - st[0][1]) / (args.steps * S), 4),
                        skipped=pn.skipped(),
                        value=round(S / ms / 1e3, 2), unit="M HOP-REC samples/s")
+        elif cfg == "skewopt":
+            S = 1 << 24
+            pn.alloc_tables(128, 1)
+            pn.init_table_glibc_offset(0, 0, 0.01)   # SPR::Init
+            total = (args.steps + 1) * S
+            ms, ph, st = [], [], []
+            for k in range(args.steps + 1):
+                pn.train_skewopt(k * S, S, total, 0.025, 10.0, 3.0, 3, 7, args.mode)
+                st.append(pn.skewopt_stats())
+                if k:
+                    ms.append(pn.last_kernel_ms())
+                    ph.append(pn.last_phase_ms()[:2])
+            ms = float(np.mean(ms))
+            passed = (st[-1][0] - st[0][0]) / (args.steps * S)
+            updated = (st[-1][1] - st[0][1]) / (args.steps * S)
+            # rows moved per sample: 18 read; written: the passed negatives and, when any passed, i and v
+            out.update(model="skewopt", dim=128, samples_per_call=S, ms_per_call=round(ms, 3),
+                       draw_update_ms=[round(float(x), 3) for x in np.mean(ph, axis=0)],
+                       gates_passed_per_sample=round(passed, 4), updated_per_sample=round(updated, 4),
+                       skipped=pn.skipped(), rows_per_s_M=round(S * (18 + passed + 2 * updated) / ms / 1e3, 1),
+                       value=round(S / ms / 1e3, 2), unit="M Skew-OPT samples/s")
         elif cfg == "c5":
             steps_, window, K, walk_times = 40, 5, 5, 1
             pn.alloc_tables(128, 2)

@@ -126,7 +126,10 @@ int smore_get_alias_encoded(const smore_ctx* ctx, int which, uint32_t* thresh, i
 
 /* ---- embedding tables ---------------------------------------------------------- */
 /* allocate W (and C when ntables == 2) as [V][dpad] fp32, dpad = dim rounded up
- * to a multiple of 4 (rows 16-byte aligned); 1 <= dim <= 512.  Tables start zeroed. */
+ * to a multiple of 4 (rows 16-byte aligned); 1 <= dim <= 512.  Tables start zeroed.
+ * ntables == 4: CSE's WU, WI, CU, CI (smore_train_cse), four [V][dpad] tables;
+ * the table accessors below (and smore_set_rows / smore_get_rows,
+ * smore_load_pretrain, smore_save_weights) then take `which` in 0..3.  3 is refused. */
 int smore_alloc_tables(smore_ctx* ctx, int dim, int ntables);
 /* replaces: the rand() initialisation in LINE/MF/BPR/DeepWalk::Init
  * (src/model/LINE.cpp:83, MF.cpp:50, BPR.cpp:49, DeepWalk.cpp:47,54):
@@ -627,6 +630,64 @@ int smore_hoprec_stats(smore_ctx* ctx, uint64_t* tested, uint64_t* passed);
  * neither the tables nor smore_skipped. */
 int smore_hoprec_records(smore_ctx* ctx, uint64_t begin, uint64_t count, int walk_steps, uint64_t seed,
                          int32_t* out, uint32_t* slots);
+
+/* replaces: NEMF::Train (src/model/NEMF.cpp:87-149; rank 0, the CLI nemf) and
+ * NERANK::Train (src/model/NERANK.cpp:87-148; rank 1, nerank) -- CSE,
+ * Collaborative Similarity Embedding -- over samples [begin, begin + count) of
+ * `total` on a FOUR-table context (smore_alloc_tables with ntables 4: tables
+ * 0..3 are WU = w_vertexU, WI = w_vertexI, CU = w_contextU, CI = w_contextI;
+ * the reference's w_contextUU / w_contextII are never touched and not kept):
+ *   v = SourceSample() until field[v] == 0;  c = TargetSample(v);
+ *   A: UpdateBatchCommunity(WI, CI, vertex c, context v, walk_steps, 5, alpha 0.05)
+ *   B: UpdateBatchCommunity(WU, CU, vertex v, context c, walk_steps, 5, alpha 0.05)
+ *   nemf:   UpdateFactorizedPair(WU, WI, v, c, reg 0.025, 5 negatives, alpha)
+ *   nerank: UpdateUIPair(WU, WI, v, c, reg 0.025, alpha): up to sixteen uniform
+ *           negatives j of c's field; the first with WU[v].(WI[c] - WI[j]) < 1
+ *           updates the three rows, then the loop breaks
+ * UpdateBatchCommunity (src/proNet.cpp:3139-3178): per step s the context (s > 0:
+ * TargetSample of the previous one; -1 ends the pass) with label 1 and five
+ * NegativeSample() with label 0, each an Opt_SigmoidRegSGD that moves its context
+ * row in place; the vertex row takes the step's summed back error at its end.
+ * Draws: stream 0, unit = sample index, the slots consumed in the order of the
+ * reference's random_gen calls (source attempts 2 slots each, TargetSample 2 or
+ * 0, NegativeSample 2, nerank's uniform indices 1 per attempt); all sixteen
+ * nerank negatives are drawn ahead, the slots after the reference's break are
+ * unused.  Differences from the reference: a rejection loop gives up after 2^16
+ * attempts; c == -1 skips the sample, a walk that hits -1 ends that pass only;
+ * each such sample counts once in smore_skipped.  Refused with SMORE_ESTATE
+ * without four tables, without fields, or when no field-0 vertex has source
+ * mass.  walk_steps in 1..10.  alpha: count from 0 (the BPR law).  Load the
+ * graph undirected with the default methods (out_degrees / degrees).  mode:
+ * SMORE_SERIAL | SMORE_ATOMIC; SMORE_HYBRID runs the atomic scatter
+ * (smore_last_mode reports SMORE_ATOMIC); SMORE_HOGWILD is refused with
+ * SMORE_EINVAL.  One GPU; C++ semantics only; not while a row census is open.
+ * A four-table context is CSE's alone: every other training, exchange, group,
+ * block, census and hot-row entry refuses it with SMORE_ESTATE. */
+int smore_train_cse(smore_ctx* ctx, int rank, uint64_t begin, uint64_t count, uint64_t total, int walk_steps,
+                    double alpha0, uint64_t seed, int mode);
+int smore_train_cse_async(smore_ctx* ctx, int rank, uint64_t begin, uint64_t count, uint64_t total, int walk_steps,
+                          double alpha0, uint64_t seed, int mode);
+/* nerank's direct term: gates tested (f evaluations) and updates made, summed
+ * over every smore_train_cse call since smore_alloc_tables (which zeroes
+ * them); nemf counts nothing; waits for the context stream */
+int smore_cse_stats(smore_ctx* ctx, uint64_t* tested, uint64_t* updated);
+/* the draws alone: the records of samples [begin, begin + count) --
+ * {v, c, A: n_00..n_04, then per step s >= 1 ctx_s, n_s0..n_s4; B: the same;
+ * the 5 (nemf) or 16 (nerank) direct negatives}, 12 walk_steps + 5 or 16 words
+ * padded to a multiple of 4, vertex ids, -1 from where a pass stopped -- into
+ * out, and (slots non-null) the Philox slots each sample consumed.  Changes
+ * neither the tables nor smore_skipped. */
+int smore_cse_records(smore_ctx* ctx, int rank, uint64_t begin, uint64_t count, int walk_steps, uint64_t seed,
+                      int32_t* out, uint32_t* slots);
+/* NEMF::Init (src/model/NEMF.cpp:62-70): tables a and b filled from ONE glibc
+ * rand() stream (seed 1, `skip` draws discarded), per element a[v][d] then
+ * b[v][d], each (rand() / RAND_MAX - 0.5) / dim */
+int smore_init_tables_glibc_pair(smore_ctx* ctx, int a, int b, uint64_t skip);
+/* NEMF::SaveWeights (src/model/NEMF.cpp:21-47): per vertex its name and the
+ * row of table table_of_field[field[v]], or the name only where that is -1
+ * (the reference: WU for field 0, WI for field 1, nothing for any other).
+ * nfields >= the context's field count.  fmt 0 (%g) or 1 (%.6f). */
+int smore_save_weights_fields(const smore_ctx* ctx, const int* table_of_field, int nfields, const char* path, int fmt);
 
 /* replaces: proNet::UpdatePairs (src/proNet.cpp:2741-2753) and Go
  * (*ProNet).UpdatePairs (pkg/pronet/optimizer.go:8-18): UpdatePair for each

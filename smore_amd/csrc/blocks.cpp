@@ -466,6 +466,7 @@ int smore_block_setup(smore_ctx* c, int model, int nparts, int part, int K, int 
         return fail(c, SMORE_EINVAL, "block schedule: bad K / mode");
     if (c->semantics != SMORE_SEM_CPP) return fail(c, SMORE_EINVAL, "block schedule: C++ rules only");
     if (c->ntables < 2) return fail(c, SMORE_ESTATE, "block schedule: W and C tables needed");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if ((rc = set_device(c))) return rc;
     const bool walk = model == SMORE_CENSUS;
     if (nparts == 1) {

@@ -62,8 +62,8 @@ void smore_destroy(smore_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
     }
     dfree(c->d_offsets); dfree(c->d_targets); dfree(c->d_vtab); dfree(c->d_ntab); dfree(c->d_ctab);
-    dfree(c->d_sig); dfree(c->d_skipped); dfree(c->d_work); dfree(c->d_warp_stats); dfree(c->d_field); dfree(c->d_hoprec_slots); dfree(c->d_hoprec_stats); dfree(c->d_skewopt_stats);
-    dfree(c->d_table[0]); dfree(c->d_table[1]);
+    dfree(c->d_sig); dfree(c->d_skipped); dfree(c->d_work); dfree(c->d_warp_stats); dfree(c->d_field); dfree(c->d_hoprec_slots); dfree(c->d_hoprec_stats); dfree(c->d_skewopt_stats); dfree(c->d_cse_stats);
+    for (float*& t : c->d_table) dfree(t);
 
     dfree(c->d_order); dfree(c->d_walks); dfree(c->d_lens); dfree(c->d_tcum); dfree(c->d_wts); dfree(c->d_nbr_sorted); dfree(c->d_ntype); dfree(c->d_ttargets); dfree(c->d_toff); dfree(c->d_paths); dfree(c->d_path_off); dfree(c->d_t_off); dfree(c->d_t_tgt); dfree(c->d_t_ts); dfree(c->d_t_min); dfree(c->d_t_max); dfree(c->d_sh_hash); dfree(c->d_sh_ids);
     dfree(c->d_rec); dfree(c->d_vt32); dfree(c->d_ct16); dfree(c->d_split);
@@ -259,11 +259,11 @@ int smore_get_alias_encoded(const smore_ctx* c, int which, uint32_t* thresh, int
 int smore_alloc_tables(smore_ctx* c, int dim, int ntables) {
     if (!c) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
-    if (dim <= 0 || dim > 512 || ntables < 1 || ntables > 2) return fail(c, SMORE_EINVAL, "bad dim/ntables");
+    if (dim <= 0 || dim > 512 || (ntables != 1 && ntables != 2 && ntables != 4))
+        return fail(c, SMORE_EINVAL, "bad dim/ntables (1, 2, or 4: the CSE tables WU, WI, CU, CI)");
     int rc;
     if ((rc = set_device(c))) return rc;
-    dfree(c->d_table[0]);
-    dfree(c->d_table[1]);
+    for (float*& t : c->d_table) dfree(t);
     c->dim = dim;
     c->dpad = (dim + 3) / 4 * 4;
     c->ntables = ntables;
@@ -295,6 +295,7 @@ int smore_alloc_tables(smore_ctx* c, int dim, int ntables) {
     if (c->d_warp_stats) HIPCHK(c, hipMemset(c->d_warp_stats, 0, 2 * sizeof(unsigned long long)));
     if (c->d_hoprec_stats) HIPCHK(c, hipMemset(c->d_hoprec_stats, 0, 2 * sizeof(unsigned long long)));
     if (c->d_skewopt_stats) HIPCHK(c, hipMemset(c->d_skewopt_stats, 0, 2 * sizeof(unsigned long long)));
+    if (c->d_cse_stats) HIPCHK(c, hipMemset(c->d_cse_stats, 0, 2 * sizeof(unsigned long long)));
     return SMORE_OK;
 }
 
@@ -586,6 +587,7 @@ int smore_set_temporal_edges(smore_ctx* c, int64_t E, const int32_t* src, const 
 // ---------------------------------------------------------------- row census
 int smore_census_begin(smore_ctx* c) {
     if (!c) return SMORE_EINVAL;
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     int rc;
     if ((rc = set_device(c))) return rc;

@@ -50,12 +50,13 @@ struct smore_ctx {
                                         // source law: smore_set_alias, smore_set_semantics), 0 no, 1 yes
     int64_t field_lines = 0, field_unknown = 0;   // smore_load_field_meta: lines read, names not in the graph
     int32_t* d_field = nullptr;
-    uint32_t* d_hoprec_slots = nullptr; // smore_hoprec_records: slots per sample
+    uint32_t* d_hoprec_slots = nullptr; // smore_hoprec_records / smore_cse_records: slots per sample
     size_t hoprec_slots_cap = 0;
     unsigned long long* d_hoprec_stats = nullptr;
+    unsigned long long* d_cse_stats = nullptr;   // CSE: nerank {gates tested, updates made} (smore_cse_stats)
     unsigned long long* d_skewopt_stats = nullptr;   // Skew-OPT: {gates passed, samples that updated} (smore_skewopt_stats)
     // tables
-    float* d_table[2] = {nullptr, nullptr};
+    float* d_table[4] = {nullptr, nullptr, nullptr, nullptr};   // ntables 4 (CSE): WU, WI, CU, CI
     int dim = 0, dpad = 0, ntables = 0;
     // hybrid scatter: hot-row bitmaps (1 bit per row), keyed by what built them
     double hot_tau = -1.0;               // < 0: the per-path default (HOT_TAU_EDGE / HOT_TAU_WALK)
@@ -390,6 +391,13 @@ inline DevGraph dev_graph(const smore_ctx* c) {
     d.ct16 = c->packed_ok ? c->d_ct16 : nullptr;
     d.V = (uint32_t)c->g->V;
     return d;
+}
+
+// a four-table context (CSE: WU, WI, CU, CI) is trained by smore_train_cse alone:
+// every other training, exchange, block, census and hot-row entry refuses it
+inline int refuse_cse(smore_ctx* c) {
+    return c && c->ntables == 4 ? fail(c, SMORE_ESTATE, "a four-table (CSE) context: only smore_train_cse trains it")
+                                : SMORE_OK;
 }
 
 inline float* table_ptr(smore_ctx* c, int which) {

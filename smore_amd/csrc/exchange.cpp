@@ -112,6 +112,7 @@ static int ensure_exchange(smore_ctx* c) {
 
 static int check_comm(smore_ctx* c) {
     if (!c) return SMORE_EINVAL;
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (!c->comm) return fail(c, SMORE_ESTATE, "no communicator (smore_comm_init / smore_group_create)");
     if (c->ntables < 1 || !c->d_table[0]) return fail(c, SMORE_ESTATE, "tables not allocated");
     return ensure_exchange(c);
@@ -338,6 +339,7 @@ int smore_exchange_set_adaptive(smore_ctx* c, int model, int K, double updates, 
     if (!c || !(updates > 0.0) || !(c0 > 0.0)) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (c->ntables < 1) return fail(c, SMORE_ESTATE, "tables not allocated");
+    if (int rc_ = refuse_cse(c)) return rc_;
     // the scales depend on the world size: only after smore_comm_init
     if (!c->comm) return fail(c, SMORE_ESTATE, "adaptive exchange before smore_comm_init");
     // an in-flight exchange's end applies the scales it was begun with

@@ -578,6 +578,8 @@ int smore_group_set_temporal_edges(smore_group* g, int64_t E, const int32_t* src
 
 int smore_group_alloc_tables(smore_group* g, int dim, int ntables) {
     if (!g) return SMORE_EINVAL;
+    if (ntables == 4 && !g->ctx.empty())   // CSE runs on one context
+        return gfail(g, 0, fail(g->ctx[0], SMORE_ESTATE, "a group has no four-table (CSE) contexts"));
     for (size_t r = 0; r < g->ctx.size(); ++r) {
         int rc = smore_alloc_tables(g->ctx[r], dim, ntables);
         if (rc) return gfail(g, (int)r, rc);

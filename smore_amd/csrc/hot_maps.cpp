@@ -351,6 +351,7 @@ extern "C" {
 
 int smore_set_hot_threshold(smore_ctx* c, double tau) {
     if (!c || tau != tau) return SMORE_EINVAL;
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (tau < 0) tau = -1.0;   // the per-path defaults
     c->hot_tau = tau;
     return SMORE_OK;
@@ -358,6 +359,7 @@ int smore_set_hot_threshold(smore_ctx* c, double tau) {
 
 int smore_set_write_combine(smore_ctx* c, int rows, int flush_rounds) {
     if (!c || rows < 0 || rows > 1024 || flush_rounds < 0) return SMORE_EINVAL;
+    if (int rc_ = refuse_cse(c)) return rc_;
     c->sh_max = rows;
     c->sh_flush = flush_rounds;
     c->hot_key.clear();
@@ -378,6 +380,7 @@ int smore_write_combine_info(const smore_ctx* c, int* rows, int* flush_rounds) {
 int smore_row_rates(smore_ctx* c, int model, int K, int which, int64_t n, double* rate) {
     if (!c || !rate || which < 0 || which > 1 || ((model < 0 || model > 3) && model != SMORE_CENSUS) || K < 0)
         return SMORE_EINVAL;
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     const int64_t V = c->g->V;
     if (n != V) return fail(c, SMORE_EINVAL, "row_rates: n must be the vertex count");
@@ -399,6 +402,7 @@ int smore_row_rates(smore_ctx* c, int model, int K, int which, int64_t n, double
 int smore_hot_row_ids(smore_ctx* c, int model, int K, int which, int64_t n, int32_t* ids) {
     if (!c || !ids || n < 0 || which < 0 || which > 1 || ((model < 0 || model > 3) && model != SMORE_CENSUS) || K < 0)
         return SMORE_EINVAL;
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     const int64_t V = c->g->V;
     if (n > V) return fail(c, SMORE_EINVAL, "more hot rows than vertices");

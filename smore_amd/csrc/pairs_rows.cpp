@@ -78,25 +78,26 @@ static int rows_io_async(smore_ctx* c, int which, const int32_t* ids, int64_t n,
     int rc;
     if ((rc = check_table(c, which))) return rc;
     if (n == 0) return SMORE_OK;
+    const int slot = which & 1;   // a four-table context's tables 2, 3 share the two buffer slots
     for (int64_t i = 0; i < n; ++i)
         if (ids[i] < 0 || ids[i] >= c->g->V) return fail(c, SMORE_EINVAL, "row id out of range");
     if ((rc = set_device(c))) return rc;
-    if (c->io_cap[which] < (size_t)n) {
+    if (c->io_cap[slot] < (size_t)n) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dfree(c->d_io_ids[which]);
-        dfree(c->d_io_rows[which]);
-        c->io_cap[which] = 0;
+        dfree(c->d_io_ids[slot]);
+        dfree(c->d_io_rows[slot]);
+        c->io_cap[slot] = 0;
         const size_t cap = std::max<size_t>((size_t)n, 4096);
-        HIPCHK(c, hipMalloc((void**)&c->d_io_ids[which], cap * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc((void**)&c->d_io_rows[which], cap * c->dim * sizeof(float)));
-        c->io_cap[which] = cap;
+        HIPCHK(c, hipMalloc((void**)&c->d_io_ids[slot], cap * sizeof(int32_t)));
+        HIPCHK(c, hipMalloc((void**)&c->d_io_rows[slot], cap * c->dim * sizeof(float)));
+        c->io_cap[slot] = cap;
     }
     const size_t bytes = (size_t)n * c->dim * sizeof(float);
-    HIPCHK(c, hipMemcpyAsync(c->d_io_ids[which], ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (to_table) HIPCHK(c, hipMemcpyAsync(c->d_io_rows[which], rows, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_rows_io(c->d_table[which], c->d_io_ids[which], (uint64_t)n, c->dpad, c->dim, c->d_io_rows[which],
+    HIPCHK(c, hipMemcpyAsync(c->d_io_ids[slot], ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (to_table) HIPCHK(c, hipMemcpyAsync(c->d_io_rows[slot], rows, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_rows_io(c->d_table[which], c->d_io_ids[slot], (uint64_t)n, c->dpad, c->dim, c->d_io_rows[slot],
                              to_table ? 1 : 0, c->stream));
-    if (!to_table) HIPCHK(c, hipMemcpyAsync(rows, c->d_io_rows[which], bytes, hipMemcpyDeviceToHost, c->stream));
+    if (!to_table) HIPCHK(c, hipMemcpyAsync(rows, c->d_io_rows[slot], bytes, hipMemcpyDeviceToHost, c->stream));
     return SMORE_OK;
 }
 
@@ -322,6 +323,7 @@ int smore_train_pairs_rows_mt(smore_ctx* c, const int32_t* v, const int32_t* cc,
         (nc > 0 && (!c_ids || !c_rows)))
         return SMORE_EINVAL;
     if (!c->has_graph || c->ntables < 2 || c->dim <= 0) return fail(c, SMORE_ESTATE, "pairs: no graph or tables");
+    if (int rc_ = refuse_cse(c)) return rc_;
     const int64_t V = c->g->V;
     for (int64_t i = 0; i < nw; ++i)
         if (w_ids[i] < 0 || w_ids[i] >= V) return fail(c, SMORE_EINVAL, "row id out of range");

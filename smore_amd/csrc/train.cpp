@@ -155,6 +155,7 @@ int smore_train_edges_async(smore_ctx* c, int model, uint64_t begin, uint64_t co
         return fail(c, SMORE_EINVAL, "bad model/mode/K");
     const int need_tables = model == SMORE_LINE2 ? 2 : 1;
     if (c->ntables < need_tables) return fail(c, SMORE_ESTATE, "tables not allocated");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (total == 0) return fail(c, SMORE_EINVAL, "total == 0");
     if (c->census)
         return fail(c, SMORE_ESTATE, "row census: edge models have exact rates (smore_row_rates with their model)");
@@ -366,6 +367,7 @@ static int train_walks(smore_ctx* c, int rule, uint64_t walk_begin, uint64_t wal
     if (!c) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (c->ntables < 2) return fail(c, SMORE_ESTATE, "walk models need W and C tables");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if ((!order && rule != 1) || walk_times <= 0 || walk_steps < 0 || window <= 0 || K < 0 || K > 10 || mode < 0 || mode > 3)
         return fail(c, SMORE_EINVAL, "bad DeepWalk / Walklets arguments");
     if (rule == 1 && (window_min < 0 || window_min > window))
@@ -591,6 +593,7 @@ int smore_train_app_async(smore_ctx* c, uint64_t unit_begin, uint64_t unit_end, 
     if (!c) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (c->ntables < 2) return fail(c, SMORE_ESTATE, "APP needs W and C tables");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (c->semantics == SMORE_SEM_GO) return fail(c, SMORE_EINVAL, "APP has no Go semantics");
     // jump <= 0 never ends a walk on a graph without dead ends (the reference
     // loops forever); the device walk is bounded, but reject it up front
@@ -644,6 +647,7 @@ int smore_train_hpe_async(smore_ctx* c, uint64_t begin, uint64_t count, uint64_t
     if (!c) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (c->ntables < 2) return fail(c, SMORE_ESTATE, "HPE needs W and C tables");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (c->semantics == SMORE_SEM_GO) return fail(c, SMORE_EINVAL, "HPE in Go semantics is the Go LINE-2 rule (internal/models/hpe/hpe.go:72-124): smore_train_edges with SMORE_LINE2");
     if (walk_steps < 1 || walk_steps > 4096 || K < 0 || K > 10 || mode < 0 || mode > 3 || total == 0)
         return fail(c, SMORE_EINVAL, "bad HPE arguments");
@@ -701,6 +705,7 @@ int smore_host::train_pairs_core(smore_ctx* c, const int32_t* v, const int32_t* 
     if (!c) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (c->ntables < 2) return fail(c, SMORE_ESTATE, "UpdatePairs needs W and C tables");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (n < 0 || (n > 0 && (!v || !cc)) || K < 0 || K > 10 || mode < 0 || mode > 3)
         return fail(c, SMORE_EINVAL, "bad UpdatePairs arguments");
     if (n == 0) return SMORE_OK;

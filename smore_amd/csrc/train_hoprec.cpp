@@ -12,7 +12,7 @@
 using namespace smore_host;
 
 // a field-0 vertex can come out of SourceSample: some alias entry returns it
-static bool field0_has_source_mass(const smore_ctx* c) {
+bool smore_host::field0_has_source_mass(const smore_ctx* c) {
     const HostGraph& g = *c->g;
     for (int64_t i = 0; i < g.V; ++i) {
         const AliasEntry& e = g.vtab[i];
@@ -111,6 +111,7 @@ int smore_train_hoprec_async(smore_ctx* c, uint64_t begin, uint64_t count, uint6
     if (!c) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (c->ntables < 1 || !c->d_table[0]) return fail(c, SMORE_ESTATE, "tables not allocated");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (total == 0) return fail(c, SMORE_EINVAL, "total == 0");
     if (mode < 0 || mode > 3) return fail(c, SMORE_EINVAL, "bad mode");
     if (mode == SMORE_HOGWILD)

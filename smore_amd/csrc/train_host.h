@@ -78,6 +78,9 @@ int build_hot_maps(smore_ctx* c, int model, int K, int64_t M, double tau_default
                    double w_scale = 1.0, double c_scale = 1.0);
 int ensure_packed(smore_ctx* c);
 
+// train_hoprec.cpp: a field-0 vertex can come out of SourceSample (HOP-REC and CSE start there)
+bool field0_has_source_mass(const smore_ctx* c);
+
 // ---------------------------------------------------------------- train.cpp
 // the grid of an update launch of up to `count` records through kernel k
 // (train_kernels.h update_kernel) in scatter `mode`: what the occupancy of k

@@ -268,11 +268,44 @@ struct SkewOptArgs {
     int dpad, mode;                // mode: SMORE_* scatter (2 = serial)
 };
 
+// CSE (cse_kernels.h; train_cse_<s|a>.hip): nemf (rank 0) and nerank (rank 1) train four
+// tables WU, WI, CU, CI; a sample is two neighbourhood passes of walk_steps
+// steps (A: vertex WI[c], contexts CI; B: vertex WU[v], contexts CU) and a
+// direct term on WU[v], WI[c] and 5 (nemf) or 16 (nerank) negative WI rows,
+// every id pre-drawn by cse_draw_kernel (train_cse_draw.hip)
+constexpr int CSE_NEG = 5;                   // negatives per pass step and of nemf's direct term (NEMF.cpp:108)
+constexpr int CSE_RANK_NEG = 16;             // nerank's direct negatives (src/proNet.cpp:2632)
+constexpr int CSE_MAX_STEPS = 10;            // walk_steps accepted
+constexpr uint32_t CSE_ATTEMPTS = 1u << 16;  // a rejection loop gives up after this many draws
+constexpr int cse_dneg(int rank) { return rank ? CSE_RANK_NEG : CSE_NEG; }
+// int32 words of a record {v, c, A: n_00..n_04, then per step s >= 1 ctx_s, n_s0..n_s4; B: the
+// same; the direct negatives}: 12 steps + 5 or 16, padded to whole 16-B words (plain ids, -1: none)
+constexpr int cse_width(int steps, int rank) { return (12 * steps + cse_dneg(rank) + 3) & ~3; }
+
+struct CseArgs {
+    const float* sig;              // 1001-entry fastSigmoid table
+    float* T[4];                   // WU, WI, CU, CI, [V][dpad] each
+    const int32_t* rec;            // cse_width(steps, rank) words per sample
+    unsigned long long* work;      // chunk counter, zeroed per launch
+    unsigned long long* stats;     // nerank {gates tested, updates made}, accumulated
+    uint64_t begin, count, total;
+    double alpha0;
+    int dpad, mode;                // mode: SMORE_* scatter (2 = serial)
+    int steps, rank;               // walk_steps; 0 nemf, 1 nerank
+};
+// the draws of samples [begin, begin + count): records, and (slots non-null) the Philox slots each
+// sample consumed; a sample without a target, or one of whose walks or rejection loops stopped
+// early, is counted once in *skipped
+hipError_t launch_cse_draw(const DevGraph& g, const int32_t* field, uint64_t seed, uint64_t begin, uint64_t count,
+                           int steps, int rank, int32_t* rec, uint32_t* slots, unsigned long long* skipped,
+                           hipStream_t st);
+
 // ---------------------------------------------------------------- update kernels
 // The kernels that turn records into row updates: edge_train_kernel and
 // pair_train_kernel (edge_kernels.h), go_rec_kernel and go_pair_kernel
 // (go_rec.h), warp_train_kernel (warp_kernels.h), hoprec_train_kernel
-// (hoprec_kernels.h), skewopt_train_kernel (skewopt_kernels.h).  Each takes its argument
+// (hoprec_kernels.h), skewopt_train_kernel (skewopt_kernels.h), cse_train_kernel
+// (cse_kernels.h).  Each takes its argument
 // struct as its one by-value parameter and exists per scatter MODE, KMAX
 // bucket and (G, M) lane layout.
 
@@ -282,12 +315,12 @@ struct SkewOptArgs {
 #define SMORE_FOR_EACH_GM(X) \
     X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
 
-enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt };
+enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse };
 
 // Every (family, MODE, KMAX) instantiation.  Each is built in a unit of its
 // own (train_edge_<mode>_k<KMAX>.hip, train_pair_<s|a|h><KMAX>.hip,
 // train_warp_<s|a>.hip, train_hoprec_<s|a>.hip, train_skewopt_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a
-// mode's four Go ones),
+// mode's four Go ones, train_cse_<s|a>.hip a mode's nemf and nerank: KMAX = the direct negatives),
 // so a new bucket is one line here and its .hip file.
 #define SMORE_FOR_EACH_UPDATE_KERNEL(X)                                             \
     X(Edge, MODE_STORE, 5) X(Edge, MODE_STORE, 10) X(Edge, MODE_STORE, 20)          \
@@ -304,7 +337,9 @@ enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt };
     X(GoPair, MODE_HYBRID, 5) X(GoPair, MODE_HYBRID, 10)                            \
     X(Warp, WARP_STORE, WARP_KMAX) X(Warp, WARP_ATOMIC, WARP_KMAX)                  \
     X(HopRec, MODE_STORE, HOPREC_KMAX) X(HopRec, MODE_ATOMIC, HOPREC_KMAX)          \
-    X(SkewOpt, MODE_STORE, SKEWOPT_KMAX) X(SkewOpt, MODE_ATOMIC, SKEWOPT_KMAX)
+    X(SkewOpt, MODE_STORE, SKEWOPT_KMAX) X(SkewOpt, MODE_ATOMIC, SKEWOPT_KMAX)      \
+    X(Cse, MODE_STORE, CSE_NEG) X(Cse, MODE_ATOMIC, CSE_NEG)                        \
+    X(Cse, MODE_STORE, CSE_RANK_NEG) X(Cse, MODE_ATOMIC, CSE_RANK_NEG)
 
 // The instantiation's kernel for dpad's lane layout (Edge: and the model's
 // rule), or nullptr when there is none: a (G, M) outside the list, BPR with
@@ -341,6 +376,7 @@ UpdateKernel update_kernel(UpdateFamily f, const EdgeArgs& a);
 UpdateKernel update_kernel(const WarpArgs& a);
 UpdateKernel update_kernel(const HopRecArgs& a);
 UpdateKernel update_kernel(const SkewOptArgs& a);
+UpdateKernel update_kernel(const CseArgs& a);
 
 // the one launch of the update kernels: 256 threads, `a` as the kernel's parameter
 template <class Args>

@@ -1,7 +1,7 @@
 // train_kernels.hip -- sampler / init kernels and the resolver of the update
 // kernels: update_kernel maps (family, scatter mode, K, dpad, model) to the
 // instantiation that one of the train_edge_* / train_pair_* / train_go_rec_*
-// / train_warp_* / train_hoprec_* / train_skewopt_* units exports (train_kernels.h SMORE_FOR_EACH_UPDATE_KERNEL).
+// / train_warp_* / train_hoprec_* / train_skewopt_* / train_cse_* units exports (train_kernels.h SMORE_FOR_EACH_UPDATE_KERNEL).
 
 #include "train_kernels.h"
 
@@ -103,6 +103,11 @@ UpdateKernel update_kernel(const HopRecArgs& a) {
 UpdateKernel update_kernel(const SkewOptArgs& a) {
     const int mode = a.mode == SMORE_ATOMIC ? SMORE_ATOMIC : SMORE_HOGWILD;
     return {find_symbol(KernelFamily::SkewOpt, mode, SKEWOPT_KMAX, a.dpad, 0), 0};
+}
+
+UpdateKernel update_kernel(const CseArgs& a) {
+    const int mode = a.mode == SMORE_ATOMIC ? SMORE_ATOMIC : SMORE_HOGWILD;
+    return {find_symbol(KernelFamily::Cse, mode, cse_dneg(a.rank), a.dpad, 0), 0};
 }
 
 hipError_t launch_sample(const DevGraph& g, uint64_t seed, uint64_t begin, uint64_t count, int K,

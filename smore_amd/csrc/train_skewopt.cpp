@@ -17,6 +17,7 @@ int smore_train_skewopt_async(smore_ctx* c, uint64_t begin, uint64_t count, uint
     if (!c) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (c->ntables < 1 || !c->d_table[0]) return fail(c, SMORE_ESTATE, "tables not allocated");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (total == 0) return fail(c, SMORE_EINVAL, "total == 0");
     if (mode < 0 || mode > 3) return fail(c, SMORE_EINVAL, "bad mode");
     if ((float)omega == 0.0f) return fail(c, SMORE_EINVAL, "omega == 0");

@@ -43,6 +43,7 @@ int smore_train_warp_async(smore_ctx* c, uint64_t begin, uint64_t count, uint64_
     if (!c) return SMORE_EINVAL;
     if (!c->has_graph) return fail(c, SMORE_ESTATE, "no graph");
     if (c->ntables < 1 || !c->d_table[0]) return fail(c, SMORE_ESTATE, "tables not allocated");
+    if (int rc_ = refuse_cse(c)) return rc_;
     if (total == 0) return fail(c, SMORE_EINVAL, "total == 0");
     if (mode < 0 || mode > 3) return fail(c, SMORE_EINVAL, "bad mode");
     if (c->semantics == SMORE_SEM_GO) return fail(c, SMORE_EINVAL, "WARP has no Go semantics");

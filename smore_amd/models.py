@@ -240,6 +240,59 @@ class HBPR(_EdgeModel):
         _progress(_alpha_at(total, alpha, total), 1.0, "\n")
 
 
+class _CSE(_EdgeModel):
+    """CSE, Collaborative Similarity Embedding (src/model/NEMF.{h,cpp}, NERANK.{h,cpp}): per
+    sample a field-0 source v and its target c, two neighbourhood passes of walk_steps steps
+    (UpdateBatchCommunity on WI/CI from c and on WU/CU from v, rate alpha 0.05) and a direct
+    user-item term on WU[v], WI[c].  Four tables; "hybrid" runs the atomic scatter; there is
+    no plain-store ("hogwild") scatter."""
+    rank = None
+    tag = None
+
+    def LoadFieldMeta(self, filename):
+        self.pnet.LoadFieldMeta(filename)
+
+    def Init(self, dim):
+        print("Model Setting:\n\tdimension:\t\t%d" % dim)
+        self.dim = dim
+        self.pnet.alloc_tables(dim, 4)              # WU, WI, CU, CI (zero)
+        self.pnet.init_tables_glibc_pair(0, 1, 0)   # src/model/NEMF.cpp:62-70
+
+    def Train(self, sample_times, walk_steps, alpha, workers=1, stop_after=None):
+        # stop_after (an extension, like seed): run only the first stop_after samples of the
+        # sample_times * 10^6 schedule
+        print("Model:\n\t[%s]\nLearning Parameters:" % self.tag)
+        print("\tsample_times:\t\t%d\n\talpha:\t\t\t%g\n\twalk steps:\t\t%d\n\tworkers:\t\t%d"
+              % (sample_times, alpha, walk_steps, workers))
+        print("Start Training[1]:")
+        total = int(sample_times) * 1000000
+        end = total if stop_after is None else min(total, int(stop_after))
+        done = 0
+        while done < end:
+            n = min(CHUNK, end - done)
+            self.pnet.train_cse(self.rank, done, n, total, walk_steps, alpha, self.seed, self.mode)
+            done += n
+            _progress(_alpha_at(done, alpha, total), done / total)
+        _progress(_alpha_at(end, alpha, total), end / total, "\n")
+
+    def SaveWeights(self, model_name, fmt=0):
+        # WU rows for field 0, WI rows for field 1, the name alone for any other field
+        print("Save Model:")
+        nf = max(2, self.pnet.fields[1])
+        self.pnet.save_weights_fields([0, 1] + [-1] * (nf - 2), model_name, fmt)
+        print("\tSave to <%s>" % model_name)
+
+
+class NEMF(_CSE):
+    """CSE with the factorisation direct term (UpdateFactorizedPair; the CLI nemf)."""
+    rank, tag = 0, "NEMF"
+
+
+class NERANK(_CSE):
+    """CSE with the ranking direct term (UpdateUIPair; the CLI nerank)."""
+    rank, tag = 1, "NERANK"
+
+
 class DeepWalk(_EdgeModel):
     """DeepWalk (src/model/DeepWalk.{h,cpp}): random walks + skip-gram pairs."""
 

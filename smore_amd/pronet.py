@@ -13,6 +13,11 @@ from . import _lib
 from ._lib import check, lib, ptr
 
 
+def _cse_rank(rank):
+    """0 / "nemf" or 1 / "nerank"."""
+    return {"nemf": 0, "nerank": 1}.get(rank, rank) if isinstance(rank, str) else int(rank)
+
+
 class ProNet:
     """Graph + alias tables + embedding tables on one GPU.
 
@@ -556,6 +561,41 @@ class ProNet:
         self._chk(lib.smore_hoprec_records(self.ctx, int(begin), int(count), int(walk_steps), int(seed), ptr(out),
                                            ptr(slots)), "hoprec_records")
         return out, slots
+
+    def train_cse(self, rank, begin, count, total, walk_steps, alpha0, seed=1, mode="atomic", sync=True):
+        """NEMF::Train (rank 0 / "nemf") or NERANK::Train (rank 1 / "nerank") over samples
+        [begin, begin + count) of total, on the four tables WU, WI, CU, CI (alloc_tables(dim, 4))."""
+        fn = lib.smore_train_cse if sync else lib.smore_train_cse_async
+        self._chk(fn(self.ctx, _cse_rank(rank), int(begin), int(count), int(total), int(walk_steps), float(alpha0),
+                     int(seed), _lib.MODE[mode]), "train_cse")
+
+    def cse_stats(self):
+        """(nerank gates tested, nerank updates made) of the CSE calls since alloc_tables."""
+        t, u = C.c_uint64(), C.c_uint64()
+        self._chk(lib.smore_cse_stats(self.ctx, C.byref(t), C.byref(u)), "cse_stats")
+        return t.value, u.value
+
+    def cse_records(self, rank, begin, count, walk_steps, seed):
+        """The draws of samples [begin, begin + count): (records [count][12 walk_steps + 5
+        (nemf) or 16 (nerank), padded to 4] of vertex ids, -1 from where a pass stopped;
+        slots consumed)."""
+        rank = _cse_rank(rank)
+        rw = (12 * int(walk_steps) + (16 if rank else 5) + 3) // 4 * 4
+        out = np.zeros((int(count), rw), np.int32)
+        slots = np.zeros(int(count), np.uint32)
+        self._chk(lib.smore_cse_records(self.ctx, rank, int(begin), int(count), int(walk_steps), int(seed), ptr(out),
+                                        ptr(slots)), "cse_records")
+        return out, slots
+
+    def init_tables_glibc_pair(self, a, b, skip=0):
+        """Tables a and b from one interleaved rand() stream (NEMF::Init)."""
+        self._chk(lib.smore_init_tables_glibc_pair(self.ctx, int(a), int(b), int(skip)), "init_tables_glibc_pair")
+
+    def save_weights_fields(self, table_of_field, path, fmt=0):
+        """Per vertex the row of table table_of_field[field[v]] (-1: the name only)."""
+        t = np.ascontiguousarray(table_of_field, np.int32)
+        self._chk(lib.smore_save_weights_fields(self.ctx, ptr(t), len(t), path.encode(), int(fmt)),
+                  "save_weights_fields")
 
     def set_semantics(self, semantics):
         """"cpp" (src/proNet.cpp rules, default) or "go" (pkg/pronet rules)."""

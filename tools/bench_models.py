@@ -25,6 +25,12 @@ calls after one warmup call, inputs resident in HBM.
        SPR::Init's table (M Skew-OPT samples/s and M rows/s: 18 rows read per
        sample plus the rows written, from smore_skewopt_stats; "hybrid" runs
        the atomic scatter, there is no plain-store one)
+  cse  CSE (nemf, then nerank) on c3's graph loaded undirected, d=128,
+       walk_steps 5, fields from the generator's user / item split, NEMF::Init's
+       tables (M CSE samples/s and M rows/s: per sample 2 + 12 walk_steps rows
+       read and added, plus nemf's 5 read and added or nerank's 8 or 16 read
+       and its one added when a gate passes; draw / update ms; "hybrid" runs the atomic scatter, there is no
+       plain-store one)
 """
 import argparse
 import json
@@ -77,13 +83,13 @@ def main():
     import smore_amd
     from smore_amd import graphgen
     for cfg in args.configs:
-        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt") else cfg)
+        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt", "cse") else cfg)
         pn = smore_amd.ProNet(0)
         t0 = time.perf_counter()
         if cfg in ("c3", "warp", "hoprec", "skewopt"):
             pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() / HBPR() / SPR() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
-        if cfg == "hoprec":
-            # HBPR loads undirected (cli/hoprec.cpp:63): every line also as item -> user
+        if cfg in ("hoprec", "cse"):
+            # HBPR, NEMF and NERANK load undirected (cli/hoprec.cpp:63, cli/nemf.cpp): every line also as item -> user
             users = int(src.max()) + 1               # the generator's split: users [0, users), items after them
             assert int(dst.min()) >= users
             src, dst, w = np.concatenate([src, dst]), np.concatenate([dst, src]), np.concatenate([w, w])
@@ -144,6 +150,36 @@ def main():
                        gates_passed_per_sample=round((st[-1][1] - st[0][1]) / (args.steps * S), 4),
                        skipped=pn.skipped(),
                        value=round(S / ms / 1e3, 2), unit="M HOP-REC samples/s")
+        elif cfg == "cse":
+            S, walk_steps = 1 << 24, 5
+            pn.set_fields((np.arange(V) >= users).astype(np.int32), 2)
+            for rank, name in enumerate(("nemf", "nerank")):
+                pn.alloc_tables(128, 4)
+                pn.init_tables_glibc_pair(0, 1, 0)   # NEMF::Init
+                total = (args.steps + 1) * S
+                ms, ph, st = [], [], []
+                for k in range(args.steps + 1):
+                    pn.train_cse(rank, k * S, S, total, walk_steps, 0.025, 7, args.mode)
+                    st.append(pn.cse_stats())
+                    if k:
+                        ms.append(pn.last_kernel_ms())
+                        ph.append(pn.last_phase_ms()[:2])
+                ms = float(np.mean(ms))
+                tested = (st[-1][0] - st[0][0]) / (args.steps * S)
+                updated = (st[-1][1] - st[0][1]) / (args.steps * S)
+                # rows moved per sample: WU[v], WI[c] and 12 context rows per step read and added; the
+                # direct term reads 5 and adds 5 (nemf), or reads batches of 8 (an upper estimate from
+                # the mean gates tested) and adds the one negative that passes (nerank)
+                rows = 2 * (2 + 12 * walk_steps) + (8 * np.ceil(max(tested, 1.0) / 8) + updated if rank else 10)
+                res = dict(out, model=name, dim=128, walk_steps=walk_steps, samples_per_call=S, ms_per_call=round(ms, 3),
+                           draw_update_ms=[round(float(x), 3) for x in np.mean(ph, axis=0)],
+                           gates_tested_per_sample=round(tested, 4),
+                           updated_per_sample=round(updated, 4), rows_per_sample=round(float(rows), 2),
+                           skipped=pn.skipped(), rows_per_s_M=round(S * rows / ms / 1e3, 1), scatter=ran(pn),
+                           value=round(S / ms / 1e3, 2), unit="M CSE samples/s")
+                print(json.dumps(res), flush=True)
+            pn.close()
+            continue
         elif cfg == "skewopt":
             S = 1 << 24
             pn.alloc_tables(128, 1)

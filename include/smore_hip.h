@@ -689,6 +689,63 @@ int smore_init_tables_glibc_pair(smore_ctx* ctx, int a, int b, uint64_t skip);
  * nfields >= the context's field count.  fmt 0 (%g) or 1 (%.6f). */
 int smore_save_weights_fields(const smore_ctx* ctx, const int* table_of_field, int nfields, const char* path, int fmt);
 
+/* replaces: GCN::Train (src/model/GCN.cpp:62-117; model SMORE_CBOW_GCN, the CLI
+ * gcn) and TEXTGCN::Train (src/model/TEXTGCN.cpp:89-144; model
+ * SMORE_CBOW_TEXTGCN, textgcn) over samples [begin, begin + count) of `total`,
+ * on table 0 (w_vertex) of a one- or two-table context; w_context is never
+ * trained:
+ *   v1 = SourceSample() until field[v1] == 0;
+ *   gcn:     UpdateCBOW(vertex v1, context v1)
+ *   textgcn: v2 = TargetSample(v1); UpdateCBOW(vertex v2, context v1)
+ * UpdateCBOW (src/proNet.cpp:2868-3001): the c-set is walk_steps draws of
+ * TargetSample(context), the w-set walk_steps draws of TargetSample(vertex)
+ * (every draw from the same vertex; a vertex without out-edge gives an empty
+ * set); w_avg and c_avg are the sums of the sets' rows; one
+ * Opt_SigmoidRegSGD (:1332-1351) of w_avg against c_avg with label 1, whose
+ * context delta every c-set row takes; negative_samples times the same with
+ * label 0 on a set of walk_steps uniform field-1 vertices; last every w-set row
+ * takes the summed vertex delta.  w_avg is computed once.
+ * Draws: stream 0, unit = sample index, the slots consumed in the order of the
+ * reference's random_gen calls (source attempts 2 slots each, TargetSample 2 or
+ * 0, a uniform negative 1 per attempt).  Differences from the reference: a
+ * rejection loop gives up after 2^16 attempts; a sample whose v2 is -1 (the
+ * reference indexes row -1), whose two sets are both empty (the reference still
+ * decays the negative rows) or whose loop gave up is skipped and counts once in
+ * smore_skipped.  Refused with SMORE_ESTATE without fields, when no field-0
+ * vertex has source mass, or when no vertex has field 1 (the reference spins
+ * forever).  walk_steps in 1..10, negative_samples in 1..20, else SMORE_EINVAL.
+ * alpha: count from 0 (the BPR law).  mode: SMORE_SERIAL | SMORE_ATOMIC;
+ * SMORE_HYBRID runs the atomic scatter (smore_last_mode reports SMORE_ATOMIC);
+ * SMORE_HOGWILD is refused with SMORE_EINVAL.  One GPU; C++ semantics only; not
+ * while a row census is open; not on a four-table context. */
+#define SMORE_CBOW_GCN 0
+#define SMORE_CBOW_TEXTGCN 1
+int smore_train_cbow(smore_ctx* ctx, int model, uint64_t begin, uint64_t count, uint64_t total, int walk_steps,
+                     int negative_samples, double alpha0, double reg, uint64_t seed, int mode);
+int smore_train_cbow_async(smore_ctx* ctx, int model, uint64_t begin, uint64_t count, uint64_t total, int walk_steps,
+                           int negative_samples, double alpha0, double reg, uint64_t seed, int mode);
+/* samples whose c-set and negative ids were pairwise distinct (their rows move
+ * together) and samples run in the reference's memory order, summed over every
+ * smore_train_cbow call since smore_alloc_tables (which zeroes them); skipped
+ * samples count in neither; waits for the context stream */
+int smore_cbow_stats(smore_ctx* ctx, uint64_t* clean, uint64_t* ordered);
+/* the draws alone: the records of samples [begin, begin + count) -- {vertex,
+ * context, c-set[walk_steps], w-set[walk_steps], negative_samples x
+ * neg-set[walk_steps]}, 2 + 2 walk_steps + negative_samples walk_steps words
+ * padded to a multiple of 4, vertex ids, an empty set -1, a skipped sample all
+ * -1 -- into out, and (slots non-null) the Philox slots each sample consumed.
+ * Changes neither the tables nor smore_skipped. */
+int smore_cbow_records(smore_ctx* ctx, int model, uint64_t begin, uint64_t count, int walk_steps, int negative_samples,
+                       uint64_t seed, int32_t* out, uint32_t* slots);
+/* TEXTGCN::SaveWeights (src/model/TEXTGCN.cpp:6-57): the header counts the
+ * vertices whose field is not 1, and those alone are written: a field-0 vertex
+ * its name and the sum of table 0's rows over its out-entries (with
+ * multiplicity, in CSR order), a field-2 vertex its name and its own row, any
+ * other its name alone.  Difference: the sums are taken in double over the fp32
+ * rows.  fmt 0 (%g) or 1 (%.6f).  (GCN::SaveWeights, GCN.cpp:6-30, is
+ * smore_save_weights_fields with table_of_field = {1, 0}.) */
+int smore_save_weights_textgcn(const smore_ctx* ctx, const char* path, int fmt);
+
 /* replaces: proNet::UpdatePairs (src/proNet.cpp:2741-2753) and Go
  * (*ProNet).UpdatePairs (pkg/pronet/optimizer.go:8-18): UpdatePair for each
  * caller-supplied pair (v[i], c[i]), i = 0 .. n-1 in order, with K <= 10

@@ -1,0 +1,4 @@
+// textgcn -- the set-sum rule with vertex = TargetSample(source) (TEXTGCN); see cbow_cli.h
+#include "cbow_cli.h"
+
+int main(int argc, char** argv) { return cbow_main(argc, argv, SMORE_CBOW_TEXTGCN); }

@@ -300,12 +300,43 @@ hipError_t launch_cse_draw(const DevGraph& g, const int32_t* field, uint64_t see
                            int steps, int rank, int32_t* rec, uint32_t* slots, unsigned long long* skipped,
                            hipStream_t st);
 
+// CBOW, the set-sum rule of GCN (SMORE_CBOW_GCN) and TEXTGCN (SMORE_CBOW_TEXTGCN) (cbow_kernels.h;
+// train_cbow_<s|a>.hip): a sample scores the sum of its w-set rows against the sum of its c-set
+// rows (label 1) and of K uniform field-1 sets (label 0), every set of S rows of table 0 takes
+// one shared delta, every id pre-drawn by cbow_draw_kernel (train_cbow_draw.hip)
+constexpr int CBOW_MAX_S = 10;                // walk_steps accepted
+constexpr int CBOW_MAX_K = 20;                // negative_samples accepted
+constexpr int CBOW_BATCH = 5;                 // rows of a set gathered together (the kernels' KMAX)
+constexpr uint32_t CBOW_ATTEMPTS = 1u << 16;  // a rejection loop gives up after this many draws
+// int32 words of a record {vertex, context, c-set[S], w-set[S], K x neg-set[S]}, padded to whole
+// 16-B words (plain ids; an empty set is S times -1, a skipped sample all -1)
+constexpr int cbow_width(int S, int K) { return (2 + 2 * S + K * S + 3) & ~3; }
+
+struct CbowArgs {
+    const float* sig;              // 1001-entry fastSigmoid table
+    float* T;                      // w_vertex, [V][dpad]
+    const int32_t* rec;            // cbow_width(S, K) words per sample
+    const uint8_t* clean;          // per sample: 1 when the c-set and negative ids are pairwise distinct
+    unsigned long long* work;      // chunk counter, zeroed per launch
+    unsigned long long* stats;     // {clean samples, ordered samples}, accumulated
+    uint64_t begin, count, total;
+    double alpha0;
+    float reg;
+    int dpad, mode;                // mode: SMORE_* scatter (2 = serial)
+    int S, K;                      // walk_steps, negative_samples
+};
+// the draws of samples [begin, begin + count): records, the clean flags, and (slots non-null)
+// the Philox slots each sample consumed; a skipped sample is counted once in *skipped
+hipError_t launch_cbow_draw(const DevGraph& g, const int32_t* field, uint64_t seed, uint64_t begin, uint64_t count,
+                            int model, int S, int K, int32_t* rec, uint8_t* clean, uint32_t* slots,
+                            unsigned long long* skipped, hipStream_t st);
+
 // ---------------------------------------------------------------- update kernels
 // The kernels that turn records into row updates: edge_train_kernel and
 // pair_train_kernel (edge_kernels.h), go_rec_kernel and go_pair_kernel
 // (go_rec.h), warp_train_kernel (warp_kernels.h), hoprec_train_kernel
 // (hoprec_kernels.h), skewopt_train_kernel (skewopt_kernels.h), cse_train_kernel
-// (cse_kernels.h).  Each takes its argument
+// (cse_kernels.h), cbow_train_kernel (cbow_kernels.h).  Each takes its argument
 // struct as its one by-value parameter and exists per scatter MODE, KMAX
 // bucket and (G, M) lane layout.
 
@@ -315,12 +346,13 @@ hipError_t launch_cse_draw(const DevGraph& g, const int32_t* field, uint64_t see
 #define SMORE_FOR_EACH_GM(X) \
     X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
 
-enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse };
+enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse, Cbow };
 
 // Every (family, MODE, KMAX) instantiation.  Each is built in a unit of its
 // own (train_edge_<mode>_k<KMAX>.hip, train_pair_<s|a|h><KMAX>.hip,
 // train_warp_<s|a>.hip, train_hoprec_<s|a>.hip, train_skewopt_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a
-// mode's four Go ones, train_cse_<s|a>.hip a mode's nemf and nerank: KMAX = the direct negatives),
+// mode's four Go ones, train_cse_<s|a>.hip a mode's nemf and nerank: KMAX = the direct negatives,
+// train_cbow_<s|a>.hip: KMAX = the gather batch),
 // so a new bucket is one line here and its .hip file.
 #define SMORE_FOR_EACH_UPDATE_KERNEL(X)                                             \
     X(Edge, MODE_STORE, 5) X(Edge, MODE_STORE, 10) X(Edge, MODE_STORE, 20)          \
@@ -339,7 +371,8 @@ enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse 
     X(HopRec, MODE_STORE, HOPREC_KMAX) X(HopRec, MODE_ATOMIC, HOPREC_KMAX)          \
     X(SkewOpt, MODE_STORE, SKEWOPT_KMAX) X(SkewOpt, MODE_ATOMIC, SKEWOPT_KMAX)      \
     X(Cse, MODE_STORE, CSE_NEG) X(Cse, MODE_ATOMIC, CSE_NEG)                        \
-    X(Cse, MODE_STORE, CSE_RANK_NEG) X(Cse, MODE_ATOMIC, CSE_RANK_NEG)
+    X(Cse, MODE_STORE, CSE_RANK_NEG) X(Cse, MODE_ATOMIC, CSE_RANK_NEG)              \
+    X(Cbow, MODE_STORE, CBOW_BATCH) X(Cbow, MODE_ATOMIC, CBOW_BATCH)
 
 // The instantiation's kernel for dpad's lane layout (Edge: and the model's
 // rule), or nullptr when there is none: a (G, M) outside the list, BPR with
@@ -377,6 +410,7 @@ UpdateKernel update_kernel(const WarpArgs& a);
 UpdateKernel update_kernel(const HopRecArgs& a);
 UpdateKernel update_kernel(const SkewOptArgs& a);
 UpdateKernel update_kernel(const CseArgs& a);
+UpdateKernel update_kernel(const CbowArgs& a);
 
 // the one launch of the update kernels: 256 threads, `a` as the kernel's parameter
 template <class Args>

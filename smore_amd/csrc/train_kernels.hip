@@ -1,7 +1,7 @@
 // train_kernels.hip -- sampler / init kernels and the resolver of the update
 // kernels: update_kernel maps (family, scatter mode, K, dpad, model) to the
 // instantiation that one of the train_edge_* / train_pair_* / train_go_rec_*
-// / train_warp_* / train_hoprec_* / train_skewopt_* / train_cse_* units exports (train_kernels.h SMORE_FOR_EACH_UPDATE_KERNEL).
+// / train_warp_* / train_hoprec_* / train_skewopt_* / train_cse_* / train_cbow_* units exports (train_kernels.h SMORE_FOR_EACH_UPDATE_KERNEL).
 
 #include "train_kernels.h"
 
@@ -108,6 +108,11 @@ UpdateKernel update_kernel(const SkewOptArgs& a) {
 UpdateKernel update_kernel(const CseArgs& a) {
     const int mode = a.mode == SMORE_ATOMIC ? SMORE_ATOMIC : SMORE_HOGWILD;
     return {find_symbol(KernelFamily::Cse, mode, cse_dneg(a.rank), a.dpad, 0), 0};
+}
+
+UpdateKernel update_kernel(const CbowArgs& a) {
+    const int mode = a.mode == SMORE_ATOMIC ? SMORE_ATOMIC : SMORE_HOGWILD;
+    return {find_symbol(KernelFamily::Cbow, mode, CBOW_BATCH, a.dpad, 0), 0};
 }
 
 hipError_t launch_sample(const DevGraph& g, uint64_t seed, uint64_t begin, uint64_t count, int K,

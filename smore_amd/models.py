@@ -293,6 +293,66 @@ class NERANK(_CSE):
     rank, tag = 1, "NERANK"
 
 
+class _CBOW(_EdgeModel):
+    """The set-sum (CBOW) rule (src/model/GCN.{h,cpp}, TEXTGCN.{h,cpp}; proNet::UpdateCBOW): per
+    sample the sum of walk_steps neighbour rows of the vertex is scored against the sum of
+    walk_steps neighbour rows of the context (label 1) and against negative_samples sets of
+    walk_steps uniform field-1 rows (label 0); every row of a set takes the set's delta.
+    "hybrid" runs the atomic scatter; there is no plain-store ("hogwild") scatter."""
+    model = None
+    tag = None
+
+    def LoadFieldMeta(self, filename):
+        self.pnet.LoadFieldMeta(filename)
+
+    def Init(self, dim):
+        print("Model Setting:\n\tdimension:\t\t%d" % dim)
+        self.dim = dim
+        self.pnet.alloc_tables(dim, 2)
+        self.pnet.init_table_glibc(0, 0)                     # w_vertex, then w_context from the
+        self.pnet.init_table_glibc(1, self.pnet.MAX_vid * dim)     # same rand() stream (GCN.cpp:41-55)
+
+    def Train(self, sample_times, walk_steps, negative_samples, reg, alpha, workers=1, stop_after=None):
+        # stop_after (an extension, like seed): run only the first stop_after samples of the
+        # sample_times * 10^6 schedule
+        print("Model:\n\t[%s]\nLearning Parameters:" % self.tag)
+        print("\tsample_times:\t\t%d\n\tnegative_samples:\t%d\n\twalk_steps:\t\t%d\n\tregularization:\t\t%g\n"
+              "\talpha:\t\t\t%g\n\tworkers:\t\t%d" % (sample_times, negative_samples, walk_steps, reg, alpha, workers))
+        print("Start Training:")
+        total = int(sample_times) * 1000000
+        end = total if stop_after is None else min(total, int(stop_after))
+        done = 0
+        while done < end:
+            n = min(CHUNK, end - done)
+            self.pnet.train_cbow(self.model, done, n, total, walk_steps, negative_samples, alpha, reg, self.seed,
+                                 self.mode)
+            done += n
+            _progress(_alpha_at(done, alpha, total), done / total)
+        _progress(_alpha_at(end, alpha, total), end / total, "\n")
+
+
+class GCN(_CBOW):
+    """UpdateCBOW(vertex = context = the field-0 source) (the CLI gcn)."""
+    model, tag = 0, "GCN"
+
+    def SaveWeights(self, model_name, fmt=0):
+        # w_context rows for field 0, w_vertex rows for field 1, the name alone for any other field
+        print("Save Model:")
+        nf = max(2, self.pnet.fields[1])
+        self.pnet.save_weights_fields([1, 0] + [-1] * (nf - 2), model_name, fmt)
+        print("\tSave to <%s>" % model_name)
+
+
+class TEXTGCN(_CBOW):
+    """UpdateCBOW(vertex = TargetSample(source), context = the field-0 source) (the CLI textgcn)."""
+    model, tag = 1, "TEXTGCN"
+
+    def SaveWeights(self, model_name, fmt=0):
+        print("Save Model:")
+        self.pnet.save_weights_textgcn(model_name, fmt)
+        print("\tSave to <%s>" % model_name)
+
+
 class DeepWalk(_EdgeModel):
     """DeepWalk (src/model/DeepWalk.{h,cpp}): random walks + skip-gram pairs."""
 

@@ -18,6 +18,11 @@ def _cse_rank(rank):
     return {"nemf": 0, "nerank": 1}.get(rank, rank) if isinstance(rank, str) else int(rank)
 
 
+def _cbow_model(model):
+    """0 / "gcn" or 1 / "textgcn"."""
+    return {"gcn": 0, "textgcn": 1}.get(model, model) if isinstance(model, str) else int(model)
+
+
 class ProNet:
     """Graph + alias tables + embedding tables on one GPU.
 
@@ -586,6 +591,36 @@ class ProNet:
         self._chk(lib.smore_cse_records(self.ctx, rank, int(begin), int(count), int(walk_steps), int(seed), ptr(out),
                                         ptr(slots)), "cse_records")
         return out, slots
+
+    def train_cbow(self, model, begin, count, total, walk_steps, negative_samples, alpha0, reg, seed=1, mode="atomic",
+                   sync=True):
+        """GCN::Train (model 0 / "gcn") or TEXTGCN::Train (model 1 / "textgcn") over samples
+        [begin, begin + count) of total, on table 0."""
+        fn = lib.smore_train_cbow if sync else lib.smore_train_cbow_async
+        self._chk(fn(self.ctx, _cbow_model(model), int(begin), int(count), int(total), int(walk_steps),
+                     int(negative_samples), float(alpha0), float(reg), int(seed), _lib.MODE[mode]), "train_cbow")
+
+    def cbow_stats(self):
+        """(clean samples, ordered samples) of the CBOW calls since alloc_tables."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(lib.smore_cbow_stats(self.ctx, C.byref(a), C.byref(b)), "cbow_stats")
+        return a.value, b.value
+
+    def cbow_records(self, model, begin, count, walk_steps, negative_samples, seed):
+        """The draws of samples [begin, begin + count): (records [count][2 + 2 walk_steps +
+        negative_samples walk_steps, padded to 4] of vertex ids, an empty set -1, a skipped
+        sample all -1; slots consumed)."""
+        S, K = int(walk_steps), int(negative_samples)
+        out = np.zeros((int(count), (2 + 2 * S + K * S + 3) // 4 * 4), np.int32)
+        slots = np.zeros(int(count), np.uint32)
+        self._chk(lib.smore_cbow_records(self.ctx, _cbow_model(model), int(begin), int(count), S, K, int(seed),
+                                         ptr(out), ptr(slots)), "cbow_records")
+        return out, slots
+
+    def save_weights_textgcn(self, path, fmt=0):
+        """TEXTGCN::SaveWeights: field-0 vertices the sum of their out-entries' rows, field-2
+        vertices their own row, field-1 vertices left out."""
+        self._chk(lib.smore_save_weights_textgcn(self.ctx, path.encode(), int(fmt)), "save_weights_textgcn")
 
     def init_tables_glibc_pair(self, a, b, skip=0):
         """Tables a and b from one interleaved rand() stream (NEMF::Init)."""

@@ -31,6 +31,12 @@ calls after one warmup call, inputs resident in HBM.
        read and added, plus nemf's 5 read and added or nerank's 8 or 16 read
        and its one added when a gate passes; draw / update ms; "hybrid" runs the atomic scatter, there is no
        plain-store one)
+  cbow GCN, then TEXTGCN (the set-sum rule) on c3's graph loaded undirected,
+       d=128, walk_steps 5, negative_samples 5, reg 0.01, fields from the
+       generator's user / item split, GCN::Init's table (M CBOW samples/s and
+       M rows/s: per sample 2 S + K S rows read and as many added, 70 at the
+       defaults; draw / update ms; clean share from smore_cbow_stats; "hybrid"
+       runs the atomic scatter, there is no plain-store one)
 """
 import argparse
 import json
@@ -83,13 +89,13 @@ def main():
     import smore_amd
     from smore_amd import graphgen
     for cfg in args.configs:
-        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt", "cse") else cfg)
+        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt", "cse", "cbow") else cfg)
         pn = smore_amd.ProNet(0)
         t0 = time.perf_counter()
         if cfg in ("c3", "warp", "hoprec", "skewopt"):
             pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() / HBPR() / SPR() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
-        if cfg in ("hoprec", "cse"):
-            # HBPR, NEMF and NERANK load undirected (cli/hoprec.cpp:63, cli/nemf.cpp): every line also as item -> user
+        if cfg in ("hoprec", "cse", "cbow"):
+            # HBPR, NEMF, NERANK, GCN and TEXTGCN load undirected (cli/hoprec.cpp:63, cli/nemf.cpp, cli/gcn.cpp): every line also as item -> user
             users = int(src.max()) + 1               # the generator's split: users [0, users), items after them
             assert int(dst.min()) >= users
             src, dst, w = np.concatenate([src, dst]), np.concatenate([dst, src]), np.concatenate([w, w])
@@ -177,6 +183,32 @@ def main():
                            updated_per_sample=round(updated, 4), rows_per_sample=round(float(rows), 2),
                            skipped=pn.skipped(), rows_per_s_M=round(S * rows / ms / 1e3, 1), scatter=ran(pn),
                            value=round(S / ms / 1e3, 2), unit="M CSE samples/s")
+                print(json.dumps(res), flush=True)
+            pn.close()
+            continue
+        elif cfg == "cbow":
+            S, ws, K = 1 << 24, 5, 5
+            pn.set_fields((np.arange(V) >= users).astype(np.int32), 2)
+            for model, name in enumerate(("gcn", "textgcn")):
+                pn.alloc_tables(128, 1)
+                pn.init_table_glibc(0, 0)   # GCN::Init's w_vertex
+                total = (args.steps + 1) * S
+                ms, ph, st = [], [], []
+                for k in range(args.steps + 1):
+                    pn.train_cbow(model, k * S, S, total, ws, K, 0.025, 0.01, 7, args.mode)
+                    st.append(pn.cbow_stats())
+                    if k:
+                        ms.append(pn.last_kernel_ms())
+                        ph.append(pn.last_phase_ms()[:2])
+                ms = float(np.mean(ms))
+                clean = (st[-1][0] - st[0][0]) / (args.steps * S)
+                # rows moved per sample: every row of the 2 + K sets is read once and added to once
+                rows = 2 * (2 * ws + K * ws)
+                res = dict(out, model=name, dim=128, walk_steps=ws, negative_samples=K, samples_per_call=S,
+                           ms_per_call=round(ms, 3), draw_update_ms=[round(float(x), 3) for x in np.mean(ph, axis=0)],
+                           clean_share=round(clean, 4), rows_per_sample=rows, skipped=pn.skipped(),
+                           rows_per_s_M=round(S * rows / ms / 1e3, 1), scatter=ran(pn),
+                           value=round(S / ms / 1e3, 2), unit="M CBOW samples/s")
                 print(json.dumps(res), flush=True)
             pn.close()
             continue

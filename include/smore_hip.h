@@ -746,6 +746,52 @@ int smore_cbow_records(smore_ctx* ctx, int model, uint64_t begin, uint64_t count
  * smore_save_weights_fields with table_of_field = {1, 0}.) */
 int smore_save_weights_textgcn(const smore_ctx* ctx, const char* path, int fmt);
 
+/* replaces: ECO::Train (src/model/ECO.cpp:64-128; the CLI eco) over samples
+ * [begin, begin + count) of `total`, on table 0 (w_vertex) of a one- or
+ * two-table context; w_ignore is never read or written:
+ *   v1 = SourceSample() until field[v1] == 0; v2 = TargetSample(v1) (unused);
+ *   UpdateDChoice(w_vertex, w_ignore, v1, v2, dim, reg, negative_samples, alpha, 16.0)
+ * UpdateDChoice (src/proNet.cpp:2221-2341), a sampled softmax: five times
+ * c1 = TargetSample(v), c2 = TargetSample(TargetSample(c1)) and negative_samples
+ * NegativeSample() rows n_k; e = exp of each row's dot with W[v], sum = their
+ * sum; W[v]'s delta is accumulated over the five lists from
+ * (2 W[c1] e1 + W[c2] e2) / (2 e1 + e2) - (sum of rows times e) / sum - reg W[v],
+ * c1, c2 and the negatives move by their softmax terms and reg, W[v] last.
+ * Draws: stream 0, unit = sample index, the slots consumed in the order of the
+ * reference's random_gen calls (source attempts 2 slots each, TargetSample 2,
+ * NegativeSample 2, index first).  Differences from the reference: the source
+ * loop gives up after 2^16 attempts; a sample one of whose TargetSamples
+ * returns -1 (the reference indexes row -1) or whose loop gave up is skipped
+ * and counts once in smore_skipped; the exponential is exp32 (csrc/exp32.h).
+ * Refused with SMORE_ESTATE without fields or when no field-0 vertex has source
+ * mass.  negative_samples in 1..20, else SMORE_EINVAL.  alpha: count from 0 (the
+ * BPR law).  mode: SMORE_SERIAL | SMORE_ATOMIC; SMORE_HYBRID runs the atomic
+ * scatter (smore_last_mode reports SMORE_ATOMIC); SMORE_HOGWILD is refused with
+ * SMORE_EINVAL.  One GPU; C++ semantics only; not while a row census is open;
+ * not on a four-table context. */
+int smore_train_eco(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, int negative_samples, double alpha0,
+                    double reg, uint64_t seed, int mode);
+int smore_train_eco_async(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, int negative_samples,
+                          double alpha0, double reg, uint64_t seed, int mode);
+/* samples whose 1 + 5 (2 + negative_samples) ids were pairwise distinct (their
+ * rows move together) and samples run in the reference's memory order, summed
+ * over every smore_train_eco call since smore_alloc_tables (which zeroes
+ * them); skipped samples count in neither; waits for the context stream */
+int smore_eco_stats(smore_ctx* ctx, uint64_t* clean, uint64_t* ordered);
+/* the draws alone (ECO.cpp:97-100, proNet.cpp:2241-2244, :2269): the records of
+ * samples [begin, begin + count) -- {v, then five times c1, c2, n_0 ..
+ * n_{negative_samples-1}}, 1 + 5 (2 + negative_samples) words padded to a
+ * multiple of 4, vertex ids, a skipped sample all -1 -- into out, and (slots
+ * non-null) the Philox slots each sample consumed.  Changes neither the tables
+ * nor smore_skipped. */
+int smore_eco_records(smore_ctx* ctx, uint64_t begin, uint64_t count, int negative_samples, uint64_t seed, int32_t* out,
+                      uint32_t* slots);
+/* ECO::Init (src/model/ECO.cpp:41-61): element e (row-major, dim per row) of
+ * table `which` takes draw skip + e * stride of the glibc rand() stream (seed
+ * 1), as rand() / RAND_MAX - 0.5 evaluated in double and rounded once; not
+ * divided by dim.  ECO's w_vertex is (0, 0, 2): w_ignore takes the odd draws. */
+int smore_init_table_glibc_unscaled(smore_ctx* ctx, int which, uint64_t skip, uint64_t stride);
+
 /* replaces: proNet::UpdatePairs (src/proNet.cpp:2741-2753) and Go
  * (*ProNet).UpdatePairs (pkg/pronet/optimizer.go:8-18): UpdatePair for each
  * caller-supplied pair (v[i], c[i]), i = 0 .. n-1 in order, with K <= 10

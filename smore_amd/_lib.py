@@ -159,6 +159,11 @@ def _load():
         "smore_cbow_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),
         "smore_cbow_records": (i32, [P, i32, u64, u64, i32, i32, u64, P, P]),
         "smore_save_weights_textgcn": (i32, [P, C.c_char_p, i32]),
+        "smore_train_eco": (i32, [P, u64, u64, u64, i32, dbl, dbl, u64, i32]),
+        "smore_train_eco_async": (i32, [P, u64, u64, u64, i32, dbl, dbl, u64, i32]),
+        "smore_eco_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),
+        "smore_eco_records": (i32, [P, u64, u64, i32, u64, P, P]),
+        "smore_init_table_glibc_unscaled": (i32, [P, i32, u64, u64]),
         "smore_init_tables_glibc_pair": (i32, [P, i32, i32, u64]),
         "smore_save_weights_fields": (i32, [P, P, i32, C.c_char_p, i32]),
         "smore_group_train_walklets": (i32, [P, u64, u64, i32, i32, i32, i32, i32, dbl, u64, i32, u64, i32]),

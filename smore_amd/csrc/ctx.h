@@ -55,8 +55,9 @@ struct smore_ctx {
     unsigned long long* d_hoprec_stats = nullptr;
     unsigned long long* d_cse_stats = nullptr;   // CSE: nerank {gates tested, updates made} (smore_cse_stats)
     unsigned long long* d_cbow_stats = nullptr;  // CBOW: {clean samples, ordered samples} (smore_cbow_stats)
-    uint8_t* d_cbow_clean = nullptr;             // CBOW: a chunk's clean flags, beside d_rec
+    uint8_t* d_cbow_clean = nullptr;             // CBOW and ECO: a chunk's clean flags, beside d_rec
     size_t cbow_clean_cap = 0;
+    unsigned long long* d_eco_stats = nullptr;   // ECO: {clean samples, ordered samples} (smore_eco_stats)
     unsigned long long* d_skewopt_stats = nullptr;   // Skew-OPT: {gates passed, samples that updated} (smore_skewopt_stats)
     // tables
     float* d_table[4] = {nullptr, nullptr, nullptr, nullptr};   // ntables 4 (CSE): WU, WI, CU, CI

@@ -331,12 +331,43 @@ hipError_t launch_cbow_draw(const DevGraph& g, const int32_t* field, uint64_t se
                             int model, int S, int K, int32_t* rec, uint8_t* clean, uint32_t* slots,
                             unsigned long long* skipped, hipStream_t st);
 
+// ECO, the sampled-softmax choice rule (eco_kernels.h; train_eco_<s|a>.hip): a sample is ECO_LISTS
+// lists {c1, c2, n_0..n_{K-1}} around one vertex v, all rows of table 0; a list's rows move by the
+// softmax of their scores over the list, W[v] takes the lists' summed delta last; every id
+// pre-drawn by eco_draw_kernel (train_eco_draw.hip)
+constexpr int ECO_LISTS = 5;                 // lists per sample (src/proNet.cpp:2239)
+constexpr int ECO_MAX_K = 20;                // negative_samples accepted
+constexpr int ECO_BATCH = 5;                 // negative rows gathered together
+constexpr uint32_t ECO_ATTEMPTS = 1u << 16;  // the source loop gives up after this many draws
+// int32 words of a record {v, then per list c1, c2, n_0..n_{K-1}}, padded to whole 16-B words
+// (plain ids; a skipped sample all -1)
+constexpr int eco_width(int K) { return (1 + ECO_LISTS * (2 + K) + 3) & ~3; }
+
+struct EcoArgs {
+    float* T;                      // w_vertex, [V][dpad]
+    const int32_t* rec;            // eco_width(K) words per sample
+    const uint8_t* clean;          // per sample: bit 0 all its 1 + 5 (2 + K) ids are pairwise distinct, bit 1 + l: v and list l's are
+    unsigned long long* work;      // chunk counter, zeroed per launch
+    unsigned long long* stats;     // {clean samples, ordered samples}, accumulated
+    uint64_t begin, count, total;
+    double alpha0;
+    float reg;
+    int dpad, mode;                // mode: SMORE_* scatter (2 = serial)
+    int K;                         // negative_samples
+};
+// the draws of samples [begin, begin + count): records, the clean flags, and (slots non-null)
+// the Philox slots each sample consumed; a skipped sample is counted once in *skipped
+hipError_t launch_eco_draw(const DevGraph& g, const int32_t* field, uint64_t seed, uint64_t begin, uint64_t count,
+                           int K, int32_t* rec, uint8_t* clean, uint32_t* slots, unsigned long long* skipped,
+                           hipStream_t st);
+
 // ---------------------------------------------------------------- update kernels
 // The kernels that turn records into row updates: edge_train_kernel and
 // pair_train_kernel (edge_kernels.h), go_rec_kernel and go_pair_kernel
 // (go_rec.h), warp_train_kernel (warp_kernels.h), hoprec_train_kernel
 // (hoprec_kernels.h), skewopt_train_kernel (skewopt_kernels.h), cse_train_kernel
-// (cse_kernels.h), cbow_train_kernel (cbow_kernels.h).  Each takes its argument
+// (cse_kernels.h), cbow_train_kernel (cbow_kernels.h), eco_train_kernel
+// (eco_kernels.h).  Each takes its argument
 // struct as its one by-value parameter and exists per scatter MODE, KMAX
 // bucket and (G, M) lane layout.
 
@@ -346,13 +377,13 @@ hipError_t launch_cbow_draw(const DevGraph& g, const int32_t* field, uint64_t se
 #define SMORE_FOR_EACH_GM(X) \
     X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
 
-enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse, Cbow };
+enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse, Cbow, Eco };
 
 // Every (family, MODE, KMAX) instantiation.  Each is built in a unit of its
 // own (train_edge_<mode>_k<KMAX>.hip, train_pair_<s|a|h><KMAX>.hip,
 // train_warp_<s|a>.hip, train_hoprec_<s|a>.hip, train_skewopt_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a
 // mode's four Go ones, train_cse_<s|a>.hip a mode's nemf and nerank: KMAX = the direct negatives,
-// train_cbow_<s|a>.hip: KMAX = the gather batch),
+// train_cbow_<s|a>.hip: KMAX = the gather batch, train_eco_<s|a>.hip a mode's three K buckets),
 // so a new bucket is one line here and its .hip file.
 #define SMORE_FOR_EACH_UPDATE_KERNEL(X)                                             \
     X(Edge, MODE_STORE, 5) X(Edge, MODE_STORE, 10) X(Edge, MODE_STORE, 20)          \
@@ -372,7 +403,9 @@ enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse,
     X(SkewOpt, MODE_STORE, SKEWOPT_KMAX) X(SkewOpt, MODE_ATOMIC, SKEWOPT_KMAX)      \
     X(Cse, MODE_STORE, CSE_NEG) X(Cse, MODE_ATOMIC, CSE_NEG)                        \
     X(Cse, MODE_STORE, CSE_RANK_NEG) X(Cse, MODE_ATOMIC, CSE_RANK_NEG)              \
-    X(Cbow, MODE_STORE, CBOW_BATCH) X(Cbow, MODE_ATOMIC, CBOW_BATCH)
+    X(Cbow, MODE_STORE, CBOW_BATCH) X(Cbow, MODE_ATOMIC, CBOW_BATCH)                \
+    X(Eco, MODE_STORE, 5) X(Eco, MODE_STORE, 10) X(Eco, MODE_STORE, 20)             \
+    X(Eco, MODE_ATOMIC, 5) X(Eco, MODE_ATOMIC, 10) X(Eco, MODE_ATOMIC, 20)
 
 // The instantiation's kernel for dpad's lane layout (Edge: and the model's
 // rule), or nullptr when there is none: a (G, M) outside the list, BPR with
@@ -411,6 +444,7 @@ UpdateKernel update_kernel(const HopRecArgs& a);
 UpdateKernel update_kernel(const SkewOptArgs& a);
 UpdateKernel update_kernel(const CseArgs& a);
 UpdateKernel update_kernel(const CbowArgs& a);
+UpdateKernel update_kernel(const EcoArgs& a);
 
 // the one launch of the update kernels: 256 threads, `a` as the kernel's parameter
 template <class Args>

@@ -353,6 +353,44 @@ class TEXTGCN(_CBOW):
         print("\tSave to <%s>" % model_name)
 
 
+class ECO(_EdgeModel):
+    """ECO (src/model/ECO.{h,cpp}; proNet::UpdateDChoice), a sampled softmax: per sample a
+    field-0 source v and five lists of two positives (a neighbour and a three-step neighbour of
+    v) and negative_samples negatives; every row moves by its softmax term over its list, W[v] by
+    the lists' summed delta.  "hybrid" runs the atomic scatter; there is no plain-store
+    ("hogwild") scatter."""
+
+    def __init__(self, device=0, mode="hybrid", seed=1):
+        super().__init__(device, mode, seed)
+        self.pnet.SetNegativeMethod("no_degrees")   # src/model/ECO.cpp:4-7
+
+    def LoadFieldMeta(self, filename):
+        self.pnet.LoadFieldMeta(filename)
+
+    def Init(self, dim):
+        print("Model Setting:\n\tdimension:\t\t%d" % dim)
+        self.dim = dim
+        self.pnet.alloc_tables(dim, 1)
+        self.pnet.init_table_glibc_unscaled(0, 0, 2)   # w_ignore takes the odd draws (ECO.cpp:54-58)
+
+    def Train(self, sample_times, negative_samples, alpha, reg, workers=1, stop_after=None):
+        # stop_after (an extension, like seed): run only the first stop_after samples of the
+        # sample_times * 10^6 schedule
+        print("Model:\n\t[ECO]\nLearning Parameters:")
+        print("\tsample_times:\t\t%d\n\tnegative_samples:\t%d\n\talpha:\t\t\t%g\n\tregularization:\t\t%g\n"
+              "\tworkers:\t\t%d" % (sample_times, negative_samples, alpha, reg, workers))
+        print("Start Training:")
+        total = int(sample_times) * 1000000
+        end = total if stop_after is None else min(total, int(stop_after))
+        done = 0
+        while done < end:
+            n = min(CHUNK, end - done)
+            self.pnet.train_eco(done, n, total, negative_samples, alpha, reg, self.seed, self.mode)
+            done += n
+            _progress(_alpha_at(done, alpha, total), done / total)
+        _progress(_alpha_at(end, alpha, total), end / total, "\n")
+
+
 class DeepWalk(_EdgeModel):
     """DeepWalk (src/model/DeepWalk.{h,cpp}): random walks + skip-gram pairs."""
 

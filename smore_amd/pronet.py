@@ -622,6 +622,35 @@ class ProNet:
         vertices their own row, field-1 vertices left out."""
         self._chk(lib.smore_save_weights_textgcn(self.ctx, path.encode(), int(fmt)), "save_weights_textgcn")
 
+    def train_eco(self, begin, count, total, negative_samples, alpha0, reg, seed=1, mode="atomic", sync=True):
+        """ECO::Train (the sampled-softmax choice rule) over samples [begin, begin + count) of
+        total, on table 0."""
+        fn = lib.smore_train_eco if sync else lib.smore_train_eco_async
+        self._chk(fn(self.ctx, int(begin), int(count), int(total), int(negative_samples), float(alpha0), float(reg),
+                     int(seed), _lib.MODE[mode]), "train_eco")
+
+    def eco_stats(self):
+        """(clean samples, ordered samples) of the ECO calls since alloc_tables."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(lib.smore_eco_stats(self.ctx, C.byref(a), C.byref(b)), "eco_stats")
+        return a.value, b.value
+
+    def eco_records(self, begin, count, negative_samples, seed):
+        """The draws of samples [begin, begin + count): (records [count][1 + 5 (2 +
+        negative_samples), padded to 4] of vertex ids, a skipped sample all -1; slots consumed)."""
+        K = int(negative_samples)
+        out = np.zeros((int(count), (1 + 5 * (2 + K) + 3) // 4 * 4), np.int32)
+        slots = np.zeros(int(count), np.uint32)
+        self._chk(lib.smore_eco_records(self.ctx, int(begin), int(count), K, int(seed), ptr(out), ptr(slots)),
+                  "eco_records")
+        return out, slots
+
+    def init_table_glibc_unscaled(self, which, skip=0, stride=1):
+        """Table `which` from every stride-th rand() draw from `skip` on, rand() / RAND_MAX - 0.5
+        (ECO::Init: (0, 0, 2))."""
+        self._chk(lib.smore_init_table_glibc_unscaled(self.ctx, int(which), int(skip), int(stride)),
+                  "init_table_glibc_unscaled")
+
     def init_tables_glibc_pair(self, a, b, skip=0):
         """Tables a and b from one interleaved rand() stream (NEMF::Init)."""
         self._chk(lib.smore_init_tables_glibc_pair(self.ctx, int(a), int(b), int(skip)), "init_tables_glibc_pair")

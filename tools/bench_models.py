@@ -37,6 +37,12 @@ calls after one warmup call, inputs resident in HBM.
        M rows/s: per sample 2 S + K S rows read and as many added, 70 at the
        defaults; draw / update ms; clean share from smore_cbow_stats; "hybrid"
        runs the atomic scatter, there is no plain-store one)
+  eco  ECO (the sampled-softmax choice rule) on c3's graph loaded undirected,
+       d=128, negative_samples 5, reg 0.01, fields from the generator's user /
+       item split, uniform negatives, ECO::Init's table (M ECO samples/s and M
+       rows/s: per sample 1 + 5 (2 + K) rows read and as many added, 72 at the
+       defaults; draw / update ms; clean share from smore_eco_stats; "hybrid"
+       runs the atomic scatter, there is no plain-store one)
 """
 import argparse
 import json
@@ -89,12 +95,12 @@ def main():
     import smore_amd
     from smore_amd import graphgen
     for cfg in args.configs:
-        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt", "cse", "cbow") else cfg)
+        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt", "cse", "cbow", "eco") else cfg)
         pn = smore_amd.ProNet(0)
         t0 = time.perf_counter()
-        if cfg in ("c3", "warp", "hoprec", "skewopt"):
-            pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() / HBPR() / SPR() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
-        if cfg in ("hoprec", "cse", "cbow"):
+        if cfg in ("c3", "warp", "hoprec", "skewopt", "eco"):
+            pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() / HBPR() / SPR() / ECO() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
+        if cfg in ("hoprec", "cse", "cbow", "eco"):
             # HBPR, NEMF, NERANK, GCN and TEXTGCN load undirected (cli/hoprec.cpp:63, cli/nemf.cpp, cli/gcn.cpp): every line also as item -> user
             users = int(src.max()) + 1               # the generator's split: users [0, users), items after them
             assert int(dst.min()) >= users
@@ -210,6 +216,31 @@ def main():
                            rows_per_s_M=round(S * rows / ms / 1e3, 1), scatter=ran(pn),
                            value=round(S / ms / 1e3, 2), unit="M CBOW samples/s")
                 print(json.dumps(res), flush=True)
+            pn.close()
+            continue
+        elif cfg == "eco":
+            S, K = 1 << 24, 5
+            pn.set_fields((np.arange(V) >= users).astype(np.int32), 2)
+            pn.alloc_tables(128, 1)
+            pn.init_table_glibc_unscaled(0, 0, 2)   # ECO::Init's w_vertex
+            total = (args.steps + 1) * S
+            ms, ph, st = [], [], []
+            for k in range(args.steps + 1):
+                pn.train_eco(k * S, S, total, K, 0.025, 0.01, 7, args.mode)
+                st.append(pn.eco_stats())
+                if k:
+                    ms.append(pn.last_kernel_ms())
+                    ph.append(pn.last_phase_ms()[:2])
+            ms = float(np.mean(ms))
+            clean = (st[-1][0] - st[0][0]) / (args.steps * S)
+            # rows moved per sample: W[v] and every row of the five lists is read once and added to once
+            rows = 2 * (1 + 5 * (2 + K))
+            res = dict(out, model="eco", dim=128, negative_samples=K, samples_per_call=S, ms_per_call=round(ms, 3),
+                       draw_update_ms=[round(float(x), 3) for x in np.mean(ph, axis=0)], clean_share=round(clean, 4),
+                       rows_per_sample=rows, skipped=pn.skipped(), finite=bool(np.isfinite(pn.get_table(0)).all()),
+                       rows_per_s_M=round(S * rows / ms / 1e3, 1), scatter=ran(pn),
+                       value=round(S / ms / 1e3, 2), unit="M ECO samples/s")
+            print(json.dumps(res), flush=True)
             pn.close()
             continue
         elif cfg == "skewopt":

@@ -1,5 +1,5 @@
 # Build of the MI355X (gfx950) hot path.  No cmake: plain make + hipcc.
-#   make            -> smore_amd/lib/libsmore_hip.so + smore_amd/bin/{line,bpr,mf,warp,hoprec,skewopt,nemf,nerank,gcn,textgcn,eco,deepwalk,...}
+#   make            -> smore_amd/lib/libsmore_hip.so + smore_amd/bin/{line,bpr,mf,warp,hoprec,skewopt,nemf,nerank,gcn,textgcn,textgcndev,eco,deepwalk,...}
 #   make oracle     -> oracle/build/liboracle.so (test infrastructure)
 #   make ref        -> oracle/_ref/ref_harness (needs /root/reference)
 #   tuning variants: make lib OBJ=build/obj_x LIB=build/x/libsmore_hip.so EXTRA=-DSMORE_WAVES_HYBRID=5
@@ -23,7 +23,7 @@ all: lib cli goshape plan_check
 
 lib: $(LIB)
 
-HOST_SRCS := host_graph loader capi hot_maps train train_warp train_hoprec train_skewopt train_cse train_cbow train_eco pairs_rows exchange group group_blocks graphgen blocks block_plan
+HOST_SRCS := host_graph loader capi hot_maps train train_warp train_hoprec train_skewopt train_cse train_cbow train_eco train_cbowdev pairs_rows exchange group group_blocks graphgen blocks block_plan
 $(OBJ)/%.o: $(SRC)/%.cpp $(HOST_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(CXXFLAGS) -c -o $@ $<
@@ -43,6 +43,7 @@ $(OBJ)/train_skewopt_s.o $(OBJ)/train_skewopt_a.o: $(SRC)/skewopt_kernels.h $(SR
 $(OBJ)/train_cse_s.o $(OBJ)/train_cse_a.o: $(SRC)/cse_kernels.h $(SRC)/hoprec_kernels.h
 $(OBJ)/train_cbow_s.o $(OBJ)/train_cbow_a.o: $(SRC)/cbow_kernels.h $(SRC)/hoprec_kernels.h
 $(OBJ)/train_eco_s.o $(OBJ)/train_eco_a.o: $(SRC)/eco_kernels.h $(SRC)/exp32.h $(SRC)/hoprec_kernels.h
+$(OBJ)/train_cbowdev_s.o $(OBJ)/train_cbowdev_a.o: $(SRC)/cbowdev_kernels.h $(SRC)/cbow_kernels.h $(SRC)/hoprec_kernels.h
 
 LIB_OBJS := $(patsubst %,$(OBJ)/%.o,$(HOST_SRCS)) $(patsubst $(SRC)/%.hip,$(OBJ)/%.o,$(wildcard $(SRC)/*.hip))
 

@@ -746,6 +746,50 @@ int smore_cbow_records(smore_ctx* ctx, int model, uint64_t begin, uint64_t count
  * smore_save_weights_fields with table_of_field = {1, 0}.) */
 int smore_save_weights_textgcn(const smore_ctx* ctx, const char* path, int fmt);
 
+/* replaces: TEXTGCNdev::Train (src/model/TEXTGCNdev.cpp:71-126; the CLI
+ * textgcndev) over samples [begin, begin + count) of `total`, on table 0
+ * (w_vertex) and table 1 (w_context) of a two-table context:
+ *   user = SourceSample() until field[user] == 0;
+ *   UpdateCBOWdev(w_vertex, w_context, user, user, dim, reg, num_events, num_words, alpha)
+ * UpdateCBOWdev (src/proNet.cpp:2755-2865): num_events times event =
+ * TargetSample(user) and num_words times word = TargetSample(event); w_avg is
+ * the sum of the words' w_context rows; then per iteration two steps on
+ * W[event] (against w_avg, against W[user]) and five pairs of steps on uniform
+ * field-1 rows; a step (Opt_SigmoidRegSGD with the row as its own loss vector)
+ * moves its row in place and accumulates the context's delta from the row as
+ * updated; last W[user] and every bag row take their accumulated deltas.  The
+ * reference's accidents are kept: `event` is the last event drawn, the label is
+ * 1 in iteration 0 only, five negative pairs whatever the flags say.
+ * A sample whose collection meets a vertex without out-edge is skipped and
+ * counted in smore_skipped (the reference returns, or indexes row -1).
+ * Alpha: the LINE schedule.  Scatter: SMORE_ATOMIC, SMORE_HYBRID (runs atomic;
+ * smore_last_mode says so) or SMORE_SERIAL; SMORE_HOGWILD is SMORE_EINVAL, and
+ * so is num_events or num_words outside 1..10.  SMORE_ESTATE without fields,
+ * without a second table, on a four-table context, when no field-0 vertex has
+ * source mass or no vertex has field 1, or while a row census is open (the
+ * rule is not counted).  One GPU, C++ semantics only (Go: SMORE_EINVAL). */
+int smore_train_cbowdev(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, int num_events, int num_words,
+                        double alpha0, double reg, uint64_t seed, int mode);
+int smore_train_cbowdev_async(smore_ctx* ctx, uint64_t begin, uint64_t count, uint64_t total, int num_events,
+                              int num_words, double alpha0, double reg, uint64_t seed, int mode);
+/* samples whose user, event and negative ids were pairwise distinct (their
+ * rows move together) and samples run in the reference's memory order, summed
+ * over every smore_train_cbowdev call since smore_alloc_tables (which zeroes
+ * them); skipped samples count in neither; waits for the context stream */
+int smore_cbowdev_stats(smore_ctx* ctx, uint64_t* clean, uint64_t* ordered);
+/* the draws alone: the records of samples [begin, begin + count) -- {user,
+ * event, bag[num_events num_words], num_events x {a0, b0, .. a4, b4}}, 2 +
+ * num_events num_words + 10 num_events words padded to a multiple of 4, vertex
+ * ids, a skipped sample all -1 -- into out, and (slots non-null) the Philox
+ * slots each sample consumed.  Changes neither the tables nor smore_skipped. */
+int smore_cbowdev_records(smore_ctx* ctx, uint64_t begin, uint64_t count, int num_events, int num_words, uint64_t seed,
+                          int32_t* out, uint32_t* slots);
+/* TEXTGCNdev::SaveWeights (src/model/TEXTGCNdev.cpp:6-39): the header counts
+ * the vertices whose field is not 1, and those alone are written: a field-0
+ * vertex its name and its table-0 row, a field-2 vertex its name and its
+ * table-1 row, any other its name alone.  fmt 0 (%g) or 1 (%.6f). */
+int smore_save_weights_textgcndev(const smore_ctx* ctx, const char* path, int fmt);
+
 /* replaces: ECO::Train (src/model/ECO.cpp:64-128; the CLI eco) over samples
  * [begin, begin + count) of `total`, on table 0 (w_vertex) of a one- or
  * two-table context; w_ignore is never read or written:

@@ -159,6 +159,11 @@ def _load():
         "smore_cbow_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),
         "smore_cbow_records": (i32, [P, i32, u64, u64, i32, i32, u64, P, P]),
         "smore_save_weights_textgcn": (i32, [P, C.c_char_p, i32]),
+        "smore_train_cbowdev": (i32, [P, u64, u64, u64, i32, i32, dbl, dbl, u64, i32]),
+        "smore_train_cbowdev_async": (i32, [P, u64, u64, u64, i32, i32, dbl, dbl, u64, i32]),
+        "smore_cbowdev_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),
+        "smore_cbowdev_records": (i32, [P, u64, u64, i32, i32, u64, P, P]),
+        "smore_save_weights_textgcndev": (i32, [P, C.c_char_p, i32]),
         "smore_train_eco": (i32, [P, u64, u64, u64, i32, dbl, dbl, u64, i32]),
         "smore_train_eco_async": (i32, [P, u64, u64, u64, i32, dbl, dbl, u64, i32]),
         "smore_eco_stats": (i32, [P, C.POINTER(u64), C.POINTER(u64)]),

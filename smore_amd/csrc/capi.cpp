@@ -62,7 +62,7 @@ void smore_destroy(smore_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
     }
     dfree(c->d_offsets); dfree(c->d_targets); dfree(c->d_vtab); dfree(c->d_ntab); dfree(c->d_ctab);
-    dfree(c->d_sig); dfree(c->d_skipped); dfree(c->d_work); dfree(c->d_warp_stats); dfree(c->d_field); dfree(c->d_hoprec_slots); dfree(c->d_hoprec_stats); dfree(c->d_skewopt_stats); dfree(c->d_cse_stats); dfree(c->d_cbow_stats); dfree(c->d_cbow_clean); dfree(c->d_eco_stats);
+    dfree(c->d_sig); dfree(c->d_skipped); dfree(c->d_work); dfree(c->d_warp_stats); dfree(c->d_field); dfree(c->d_hoprec_slots); dfree(c->d_hoprec_stats); dfree(c->d_skewopt_stats); dfree(c->d_cse_stats); dfree(c->d_cbow_stats); dfree(c->d_cbow_clean); dfree(c->d_eco_stats); dfree(c->d_cbowdev_stats);
     for (float*& t : c->d_table) dfree(t);
 
     dfree(c->d_order); dfree(c->d_walks); dfree(c->d_lens); dfree(c->d_tcum); dfree(c->d_wts); dfree(c->d_nbr_sorted); dfree(c->d_ntype); dfree(c->d_ttargets); dfree(c->d_toff); dfree(c->d_paths); dfree(c->d_path_off); dfree(c->d_t_off); dfree(c->d_t_tgt); dfree(c->d_t_ts); dfree(c->d_t_min); dfree(c->d_t_max); dfree(c->d_sh_hash); dfree(c->d_sh_ids);
@@ -298,6 +298,7 @@ int smore_alloc_tables(smore_ctx* c, int dim, int ntables) {
     if (c->d_cse_stats) HIPCHK(c, hipMemset(c->d_cse_stats, 0, 2 * sizeof(unsigned long long)));
     if (c->d_cbow_stats) HIPCHK(c, hipMemset(c->d_cbow_stats, 0, 2 * sizeof(unsigned long long)));
     if (c->d_eco_stats) HIPCHK(c, hipMemset(c->d_eco_stats, 0, 2 * sizeof(unsigned long long)));
+    if (c->d_cbowdev_stats) HIPCHK(c, hipMemset(c->d_cbowdev_stats, 0, 2 * sizeof(unsigned long long)));
     return SMORE_OK;
 }
 

@@ -50,13 +50,14 @@ struct smore_ctx {
                                         // source law: smore_set_alias, smore_set_semantics), 0 no, 1 yes
     int64_t field_lines = 0, field_unknown = 0;   // smore_load_field_meta: lines read, names not in the graph
     int32_t* d_field = nullptr;
-    uint32_t* d_hoprec_slots = nullptr; // smore_hoprec_records / smore_cse_records: slots per sample
+    uint32_t* d_hoprec_slots = nullptr; // smore_{hoprec,cse,cbow,eco,cbowdev}_records: slots per sample
     size_t hoprec_slots_cap = 0;
     unsigned long long* d_hoprec_stats = nullptr;
     unsigned long long* d_cse_stats = nullptr;   // CSE: nerank {gates tested, updates made} (smore_cse_stats)
     unsigned long long* d_cbow_stats = nullptr;  // CBOW: {clean samples, ordered samples} (smore_cbow_stats)
-    uint8_t* d_cbow_clean = nullptr;             // CBOW and ECO: a chunk's clean flags, beside d_rec
+    uint8_t* d_cbow_clean = nullptr;             // CBOW, ECO and CBOWdev: a chunk's clean flags, beside d_rec
     size_t cbow_clean_cap = 0;
+    unsigned long long* d_cbowdev_stats = nullptr;  // CBOWdev: {clean samples, ordered samples} (smore_cbowdev_stats)
     unsigned long long* d_eco_stats = nullptr;   // ECO: {clean samples, ordered samples} (smore_eco_stats)
     unsigned long long* d_skewopt_stats = nullptr;   // Skew-OPT: {gates passed, samples that updated} (smore_skewopt_stats)
     // tables

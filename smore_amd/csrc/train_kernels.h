@@ -361,13 +361,46 @@ hipError_t launch_eco_draw(const DevGraph& g, const int32_t* field, uint64_t see
                            int K, int32_t* rec, uint8_t* clean, uint32_t* slots, unsigned long long* skipped,
                            hipStream_t st);
 
+// CBOWdev, the bag-of-words event rule of TEXTGCNdev (cbowdev_kernels.h; train_cbowdev_<s|a>.hip):
+// a sample sums num_events x num_words rows of table 1 (w_context) into a bag, steps W[event]
+// and ten uniform field-1 rows of table 0 per iteration against the bag and against W[user], one
+// row at a time and in place, then W[user] and every bag row take their accumulated deltas; every
+// id pre-drawn by cbowdev_draw_kernel (train_cbowdev_draw.hip)
+constexpr int CBOWDEV_MAX = 10;                  // num_events and num_words accepted
+constexpr int CBOWDEV_NEG = 5;                   // negative pairs per iteration (the reference's constant)
+constexpr int CBOWDEV_BATCH = 5;                 // bag rows gathered together (the kernels' KMAX)
+constexpr uint32_t CBOWDEV_ATTEMPTS = 1u << 16;  // a rejection loop gives up after this many draws
+// int32 words of a record {user, event, bag[E N], E x {a0, b0, .. a4, b4}}, padded to whole 16-B
+// words (plain ids; a skipped sample all -1)
+constexpr int cbowdev_width(int E, int N) { return (2 + E * N + 2 * CBOWDEV_NEG * E + 3) & ~3; }
+
+struct CbowDevArgs {
+    const float* sig;              // 1001-entry fastSigmoid table
+    float* T;                      // w_vertex, [V][dpad]
+    float* C;                      // w_context, [V][dpad]
+    const int32_t* rec;            // cbowdev_width(E, N) words per sample
+    const uint8_t* clean;          // per sample: 1 when user, event and the negative ids are pairwise distinct
+    unsigned long long* work;      // chunk counter, zeroed per launch
+    unsigned long long* stats;     // {clean samples, ordered samples}, accumulated
+    uint64_t begin, count, total;
+    double alpha0;
+    float reg;
+    int dpad, mode;                // mode: SMORE_* scatter (2 = serial)
+    int E, N;                      // num_events, num_words
+};
+// the draws of samples [begin, begin + count): records, the clean flags, and (slots non-null)
+// the Philox slots each sample consumed; a skipped sample is counted once in *skipped
+hipError_t launch_cbowdev_draw(const DevGraph& g, const int32_t* field, uint64_t seed, uint64_t begin, uint64_t count,
+                               int E, int N, int32_t* rec, uint8_t* clean, uint32_t* slots,
+                               unsigned long long* skipped, hipStream_t st);
+
 // ---------------------------------------------------------------- update kernels
 // The kernels that turn records into row updates: edge_train_kernel and
 // pair_train_kernel (edge_kernels.h), go_rec_kernel and go_pair_kernel
 // (go_rec.h), warp_train_kernel (warp_kernels.h), hoprec_train_kernel
 // (hoprec_kernels.h), skewopt_train_kernel (skewopt_kernels.h), cse_train_kernel
 // (cse_kernels.h), cbow_train_kernel (cbow_kernels.h), eco_train_kernel
-// (eco_kernels.h).  Each takes its argument
+// (eco_kernels.h), cbowdev_train_kernel (cbowdev_kernels.h).  Each takes its argument
 // struct as its one by-value parameter and exists per scatter MODE, KMAX
 // bucket and (G, M) lane layout.
 
@@ -377,13 +410,14 @@ hipError_t launch_eco_draw(const DevGraph& g, const int32_t* field, uint64_t see
 #define SMORE_FOR_EACH_GM(X) \
     X(1, 4) X(2, 4) X(4, 4) X(8, 4) X(16, 4) X(32, 4) X(64, 4) X(64, 8)
 
-enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse, Cbow, Eco };
+enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse, Cbow, Eco, CbowDev };
 
 // Every (family, MODE, KMAX) instantiation.  Each is built in a unit of its
 // own (train_edge_<mode>_k<KMAX>.hip, train_pair_<s|a|h><KMAX>.hip,
 // train_warp_<s|a>.hip, train_hoprec_<s|a>.hip, train_skewopt_<s|a>.hip; train_go_rec_<s|a|h>.hip holds a
 // mode's four Go ones, train_cse_<s|a>.hip a mode's nemf and nerank: KMAX = the direct negatives,
-// train_cbow_<s|a>.hip: KMAX = the gather batch, train_eco_<s|a>.hip a mode's three K buckets),
+// train_cbow_<s|a>.hip: KMAX = the gather batch, train_eco_<s|a>.hip a mode's three K buckets,
+// train_cbowdev_<s|a>.hip: KMAX = the bag's gather batch),
 // so a new bucket is one line here and its .hip file.
 #define SMORE_FOR_EACH_UPDATE_KERNEL(X)                                             \
     X(Edge, MODE_STORE, 5) X(Edge, MODE_STORE, 10) X(Edge, MODE_STORE, 20)          \
@@ -405,7 +439,8 @@ enum class KernelFamily { Edge, Pair, GoRec, GoPair, Warp, HopRec, SkewOpt, Cse,
     X(Cse, MODE_STORE, CSE_RANK_NEG) X(Cse, MODE_ATOMIC, CSE_RANK_NEG)              \
     X(Cbow, MODE_STORE, CBOW_BATCH) X(Cbow, MODE_ATOMIC, CBOW_BATCH)                \
     X(Eco, MODE_STORE, 5) X(Eco, MODE_STORE, 10) X(Eco, MODE_STORE, 20)             \
-    X(Eco, MODE_ATOMIC, 5) X(Eco, MODE_ATOMIC, 10) X(Eco, MODE_ATOMIC, 20)
+    X(Eco, MODE_ATOMIC, 5) X(Eco, MODE_ATOMIC, 10) X(Eco, MODE_ATOMIC, 20)          \
+    X(CbowDev, MODE_STORE, CBOWDEV_BATCH) X(CbowDev, MODE_ATOMIC, CBOWDEV_BATCH)
 
 // The instantiation's kernel for dpad's lane layout (Edge: and the model's
 // rule), or nullptr when there is none: a (G, M) outside the list, BPR with
@@ -445,6 +480,7 @@ UpdateKernel update_kernel(const SkewOptArgs& a);
 UpdateKernel update_kernel(const CseArgs& a);
 UpdateKernel update_kernel(const CbowArgs& a);
 UpdateKernel update_kernel(const EcoArgs& a);
+UpdateKernel update_kernel(const CbowDevArgs& a);
 
 // the one launch of the update kernels: 256 threads, `a` as the kernel's parameter
 template <class Args>

@@ -1,7 +1,7 @@
 // train_kernels.hip -- sampler / init kernels and the resolver of the update
 // kernels: update_kernel maps (family, scatter mode, K, dpad, model) to the
 // instantiation that one of the train_edge_* / train_pair_* / train_go_rec_*
-// / train_warp_* / train_hoprec_* / train_skewopt_* / train_cse_* / train_cbow_* / train_eco_* units exports (train_kernels.h SMORE_FOR_EACH_UPDATE_KERNEL).
+// / train_warp_* / train_hoprec_* / train_skewopt_* / train_cse_* / train_cbow_* / train_eco_* / train_cbowdev_* units exports (train_kernels.h SMORE_FOR_EACH_UPDATE_KERNEL).
 
 #include "train_kernels.h"
 
@@ -118,6 +118,11 @@ UpdateKernel update_kernel(const CbowArgs& a) {
 UpdateKernel update_kernel(const EcoArgs& a) {
     const int mode = a.mode == SMORE_ATOMIC ? SMORE_ATOMIC : SMORE_HOGWILD;
     return {find_symbol(KernelFamily::Eco, mode, kmax_of(a.K), a.dpad, 0), 0};
+}
+
+UpdateKernel update_kernel(const CbowDevArgs& a) {
+    const int mode = a.mode == SMORE_ATOMIC ? SMORE_ATOMIC : SMORE_HOGWILD;
+    return {find_symbol(KernelFamily::CbowDev, mode, CBOWDEV_BATCH, a.dpad, 0), 0};
 }
 
 hipError_t launch_sample(const DevGraph& g, uint64_t seed, uint64_t begin, uint64_t count, int K,

@@ -353,6 +353,48 @@ class TEXTGCN(_CBOW):
         print("\tSave to <%s>" % model_name)
 
 
+class TEXTGCNdev(_EdgeModel):
+    """TEXTGCNdev (src/model/TEXTGCNdev.{h,cpp}; proNet::UpdateCBOWdev), the bag-of-words event
+    rule: per sample a field-0 user, num_events events of the user and num_words words of each;
+    the words' w_context rows are summed into a bag; W[event] and ten uniform field-1 rows per
+    iteration step against the bag and against W[user], in place; W[user] and the bag rows take
+    their accumulated deltas last.  The reference's accidents are kept.
+    "hybrid" runs the atomic scatter; there is no plain-store ("hogwild") scatter."""
+
+    def LoadFieldMeta(self, filename):
+        self.pnet.LoadFieldMeta(filename)
+
+    def Init(self, dim):
+        print("Model Setting:\n\tdimension:\t\t%d" % dim)
+        self.dim = dim
+        self.pnet.alloc_tables(dim, 2)
+        self.pnet.init_table_glibc(0, 0)                     # w_vertex whole, then w_context, from the
+        self.pnet.init_table_glibc(1, self.pnet.MAX_vid * dim)     # same rand() stream (TEXTGCNdev.cpp:41-65)
+
+    def Train(self, sample_times, num_events, num_words, reg, alpha, workers=1, stop_after=None):
+        # stop_after (an extension, like seed): run only the first stop_after samples of the
+        # sample_times * 10^6 schedule
+        print("Model:\n\t[TEXTGCNdev]\nLearning Parameters:")
+        print("\tsample_times:\t\t%d\n\tnegative_samples:\tfixed\n\tnum_events:\t%d\n\tnum_words:\t%d\n"
+              "\tregularization:\t\t%g\n\talpha:\t\t\t%g\n\tworkers:\t\t%d"
+              % (sample_times, num_events, num_words, reg, alpha, workers))
+        print("Start Training:")
+        total = int(sample_times) * 1000000
+        end = total if stop_after is None else min(total, int(stop_after))
+        done = 0
+        while done < end:
+            n = min(CHUNK, end - done)
+            self.pnet.train_cbowdev(done, n, total, num_events, num_words, alpha, reg, self.seed, self.mode)
+            done += n
+            _progress(_alpha_at(done, alpha, total), done / total)
+        _progress(_alpha_at(end, alpha, total), end / total, "\n")
+
+    def SaveWeights(self, model_name, fmt=0):
+        print("Save Model:")
+        self.pnet.save_weights_textgcndev(model_name, fmt)
+        print("\tSave to <%s>" % model_name)
+
+
 class ECO(_EdgeModel):
     """ECO (src/model/ECO.{h,cpp}; proNet::UpdateDChoice), a sampled softmax: per sample a
     field-0 source v and five lists of two positives (a neighbour and a three-step neighbour of

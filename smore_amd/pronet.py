@@ -622,6 +622,34 @@ class ProNet:
         vertices their own row, field-1 vertices left out."""
         self._chk(lib.smore_save_weights_textgcn(self.ctx, path.encode(), int(fmt)), "save_weights_textgcn")
 
+    def train_cbowdev(self, begin, count, total, num_events, num_words, alpha0, reg, seed=1, mode="atomic", sync=True):
+        """TEXTGCNdev::Train (the bag-of-words event rule) over samples [begin, begin + count)
+        of total, on tables 0 (w_vertex) and 1 (w_context)."""
+        fn = lib.smore_train_cbowdev if sync else lib.smore_train_cbowdev_async
+        self._chk(fn(self.ctx, int(begin), int(count), int(total), int(num_events), int(num_words), float(alpha0),
+                     float(reg), int(seed), _lib.MODE[mode]), "train_cbowdev")
+
+    def cbowdev_stats(self):
+        """(clean samples, ordered samples) of the CBOWdev calls since alloc_tables."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(lib.smore_cbowdev_stats(self.ctx, C.byref(a), C.byref(b)), "cbowdev_stats")
+        return a.value, b.value
+
+    def cbowdev_records(self, begin, count, num_events, num_words, seed):
+        """The draws of samples [begin, begin + count): (records [count][2 + num_events num_words
+        + 10 num_events, padded to 4] of vertex ids, a skipped sample all -1; slots consumed)."""
+        E, N = int(num_events), int(num_words)
+        out = np.zeros((int(count), (2 + E * N + 10 * E + 3) // 4 * 4), np.int32)
+        slots = np.zeros(int(count), np.uint32)
+        self._chk(lib.smore_cbowdev_records(self.ctx, int(begin), int(count), E, N, int(seed), ptr(out), ptr(slots)),
+                  "cbowdev_records")
+        return out, slots
+
+    def save_weights_textgcndev(self, path, fmt=0):
+        """TEXTGCNdev::SaveWeights: field-0 vertices their table-0 row, field-2 vertices their
+        table-1 row, field-1 vertices left out."""
+        self._chk(lib.smore_save_weights_textgcndev(self.ctx, path.encode(), int(fmt)), "save_weights_textgcndev")
+
     def train_eco(self, begin, count, total, negative_samples, alpha0, reg, seed=1, mode="atomic", sync=True):
         """ECO::Train (the sampled-softmax choice rule) over samples [begin, begin + count) of
         total, on table 0."""

@@ -43,6 +43,13 @@ calls after one warmup call, inputs resident in HBM.
        rows/s: per sample 1 + 5 (2 + K) rows read and as many added, 72 at the
        defaults; draw / update ms; clean share from smore_eco_stats; "hybrid"
        runs the atomic scatter, there is no plain-store one)
+  textgcndev TEXTGCNdev (the bag-of-words event rule) on c3's graph loaded
+       undirected, d=128, num_events 1, num_words 5, reg 0.01, fields from the
+       generator's user / item split, TEXTGCNdev::Init's tables (M CBOWdev
+       samples/s and M rows/s: per sample 2 + E N + 10 E rows read and as many
+       added, 17 and 17 at the defaults; draw / update ms; clean share from
+       smore_cbowdev_stats; "hybrid" runs the atomic scatter, there is no
+       plain-store one)
 """
 import argparse
 import json
@@ -95,12 +102,12 @@ def main():
     import smore_amd
     from smore_amd import graphgen
     for cfg in args.configs:
-        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt", "cse", "cbow", "eco") else cfg)
+        V, (src, dst, w) = graphgen.config_edges("c5" if cfg.startswith("c5") else "c3" if cfg in ("warp", "hoprec", "skewopt", "cse", "cbow", "eco", "textgcndev") else cfg)
         pn = smore_amd.ProNet(0)
         t0 = time.perf_counter()
         if cfg in ("c3", "warp", "hoprec", "skewopt", "eco"):
             pn.SetNegativeMethod("no_degrees")       # BPR() / WARP() / HBPR() / SPR() / ECO() (src/model/BPR.cpp:4-7, WARP.cpp:4-7)
-        if cfg in ("hoprec", "cse", "cbow", "eco"):
+        if cfg in ("hoprec", "cse", "cbow", "eco", "textgcndev"):
             # HBPR, NEMF, NERANK, GCN and TEXTGCN load undirected (cli/hoprec.cpp:63, cli/nemf.cpp, cli/gcn.cpp): every line also as item -> user
             users = int(src.max()) + 1               # the generator's split: users [0, users), items after them
             assert int(dst.min()) >= users
@@ -240,6 +247,34 @@ def main():
                        rows_per_sample=rows, skipped=pn.skipped(), finite=bool(np.isfinite(pn.get_table(0)).all()),
                        rows_per_s_M=round(S * rows / ms / 1e3, 1), scatter=ran(pn),
                        value=round(S / ms / 1e3, 2), unit="M ECO samples/s")
+            print(json.dumps(res), flush=True)
+            pn.close()
+            continue
+        elif cfg == "textgcndev":
+            S, E, N = 1 << 24, 1, 5
+            pn.set_fields((np.arange(V) >= users).astype(np.int32), 2)
+            pn.alloc_tables(128, 2)
+            pn.init_table_glibc(0, 0)          # TEXTGCNdev::Init: w_vertex whole, then w_context
+            pn.init_table_glibc(1, V * 128)
+            total = (args.steps + 1) * S
+            ms, ph, st = [], [], []
+            for k in range(args.steps + 1):
+                pn.train_cbowdev(k * S, S, total, E, N, 0.025, 0.01, 7, args.mode)
+                st.append(pn.cbowdev_stats())
+                if k:
+                    ms.append(pn.last_kernel_ms())
+                    ph.append(pn.last_phase_ms()[:2])
+            ms = float(np.mean(ms))
+            clean = (st[-1][0] - st[0][0]) / (args.steps * S)
+            # rows moved per sample: user, event, the bag and the negatives are read once and added to
+            # once (the event row takes 2 E adds on one read)
+            rows = 2 * (2 + E * N + 10 * E)
+            res = dict(out, model="textgcndev", dim=128, num_events=E, num_words=N, samples_per_call=S,
+                       ms_per_call=round(ms, 3), draw_update_ms=[round(float(x), 3) for x in np.mean(ph, axis=0)],
+                       clean_share=round(clean, 4), rows_per_sample=rows, skipped=pn.skipped(),
+                       finite=bool(np.isfinite(pn.get_table(0)).all() and np.isfinite(pn.get_table(1)).all()),
+                       rows_per_s_M=round(S * rows / ms / 1e3, 1), scatter=ran(pn),
+                       value=round(S / ms / 1e3, 2), unit="M CBOWdev samples/s")
             print(json.dumps(res), flush=True)
             pn.close()
             continue
